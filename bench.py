@@ -1,7 +1,11 @@
 """bench.py -- rays/s of the forward render hot path on N MI355X GPUs (one node).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times K steps and prints the headline line (value, ms_per_step, the roofline of the timed
+kernels).  --full adds everything else the line has reported (training steps, the other BASELINE configs, the CPU
+baseline, live PMC traffic, the DDP step at N > 1); --dump-outputs DIR writes the last timed step's outputs as .npy.
 
 A "step" = one pass of the hot path over one synthetic 1280x1920 frame (2,457,600 rays):
 BASELINE.json configs[1] -- proposal 64 + NeRF 128 samples, NeRF grid L=16 C=2 T=2^19, proposal grid
@@ -573,6 +577,29 @@ def fp32_step_both_engines(model, flat, device, **kw):
     return r
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_PIXELS = 1 << 20
+
+
+def dump_outputs(out, rows, cols, path):
+    """--dump-outputs: what the timed path's last step returned to its caller, as <path>/<key>.npy (float32).  Every
+    per-pixel buffer of render_image's dict ([rows, W, ...]) at one fixed sample of pixels (numpy seed 0, sorted flat
+    indices, the same for every key; the whole frame when it fits): 2^20 of the 2,457,600 pixels of the headline frame,
+    ~38 MB.  The 'ray_*' visualisation bundles (a random draw of rays per level) are not written."""
+    n_pix = rows * cols
+    keys = sorted(k for k, v in out.items() if torch.is_tensor(v) and v.dim() >= 2 and tuple(v.shape[:2]) == (rows, cols))
+    per_pixel = sum(out[k][0, 0].numel() for k in keys)
+    n = min(n_pix, DUMP_PIXELS, DUMP_MAX_BYTES // (4 * max(per_pixel, 1)))
+    idx = None if n == n_pix else torch.from_numpy(np.sort(np.random.default_rng(0).choice(n_pix, n, replace=False)))
+    os.makedirs(path, exist_ok=True)
+    for k in keys:
+        v = out[k].reshape((n_pix,) + tuple(out[k].shape[2:]))
+        if idx is not None:
+            v = v.index_select(0, idx.to(v.device))
+        np.save(os.path.join(path, k + ".npy"), v.float().cpu().numpy())
+    return dict(dir=path, keys=keys, pixels=n, of_pixels=n_pix)
+
+
 def self_launch(n):
     """Re-run this command line as N ranks: `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
     --master-port <free> bench.py <the same arguments>`.  Returns the launcher's exit code.  RCCL wants one GPU per rank:
@@ -598,9 +625,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=None, help="ranks (one per GPU); default: WORLD_SIZE when a launcher set it, else 1")
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-train", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the post-timed configs[3] / configs[4] frames and the PMC traffic passes")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the line reports: live PMC traffic, the exact-fp32 and with-weights frames, "
+                         "the training steps, the other BASELINE configs, the CPU baseline and (at N > 1) the DDP step.  Off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (its per-pixel buffers, float32, a fixed sample of pixels) as DIR/<key>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-train", action="store_true", help="with --full: skip the training steps and the per-path figures after them")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the post-timed configs[3] / configs[4] frames and the PMC traffic passes")
     ap.add_argument("--pmc-child", action="store_true", help="(internal) the short run live_traffic() profiles")
     ap.add_argument("--ray-major", action="store_true", help="lanes = consecutive samples of a ray (default: neighbouring rays)")
     ap.add_argument("--mlp-mode", type=int, default=None, help="0 fp32-input MFMA, 1 split-f16 MFMA (default: the package default)")
@@ -732,6 +764,7 @@ def main():
     if world > 1:
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
     dt = float(t.item())
+    dumped = dump_outputs(out, rows, W_IMG, args.dump_outputs) if (args.dump_outputs and rank == 0) else None
 
     # per-kernel time from the HIP events recorded on the launch stream during the timed steps
     feat_ms = {0: 0.0, 1: 0.0}; mlp_ms = {0: 0.0, 1: 0.0}; rays_seen = {0: 0, 1: 0}; launches = {0: 0, 1: 0}
@@ -762,7 +795,7 @@ def main():
                  "served mostly from L2 (TCC hit ~91 %), so it may exceed what an HBM copy reaches (hbm_probe)")
         # HBM-side bytes per launch: measured live by two rocprofv3 PMC passes over a child run of this script when
         # rocprofv3 is on PATH (live_traffic); else from the committed PMC passes of this same command
-        live = None if (args.no_extras or world > 1) else live_traffic(args.autocast)
+        live = None if (not args.full or args.no_extras or world > 1) else live_traffic(args.autocast)
         if live is not None:
             gather["traffic"] = live["fetch_bytes_per_launch"] + live["write_bytes_per_launch"]
             gather["traffic_note"] = (f"LIVE: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) over a 160-row slice rendered by a child of "
@@ -873,10 +906,13 @@ def main():
                                          algbw_GBps=exch[0][2] * world / (sum(ms) / len(ms) * 1e-3) / 1e9,
                                          note="HIP events around the frame's one packed all_gather_into_tensor on rank 0 (includes waiting "
                                               "for the slowest rank's shard)")
+        if dumped is not None:
+            res["outputs_dumped"] = dumped
+        # everything below measures something other than the headline: only with --full.
         # the CPU leg runs AFTER the training legs when both are on: its 32- and 256-thread passes leave the host busy enough
         # (thread pools, a changed torch thread count) to show in the launch-heavy training steps that followed it -- r06: 9.37 ms
         # in the line against 8.7 ms for the same step run alone on the same box (profiles/r06/bench_order_note.txt)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             flat_cpu = {k: v.reshape(n_rays, -1) for k, v in batch.items() if k != "rand_vec"}
             rgb_cpu = out["rgb"].reshape(n_rays, 3).clone()
             cpu_leg = lambda: cpu_baseline(sd, flat_cpu, rand_vec, rgb_cpu, heads=args.cfg5, eval_camidx=eval_camidx if args.cfg5 else None,
@@ -884,7 +920,7 @@ def main():
             if args.no_train or args.no_extras or args.cameras != 1 or args.cfg5:
                 res["cpu_baseline"] = cpu_leg()
                 cpu_leg = None
-        if world == 1 and not args.no_train and args.cameras == 1 and not args.cfg5:
+        if args.full and world == 1 and not args.no_train and args.cameras == 1 and not args.cfg5:
             flat = {k: v.reshape(n_rays, -1) for k, v in batch.items() if k != "rand_vec"}
             # the price of strict fp32 in the headline: the same frame with the exact-fp32 MFMA dense layers (--mlp-mode 0)
             if model.nerf_mlp.mlp_mode != 0:
@@ -982,7 +1018,7 @@ def main():
                 }
     if rank == 0 and world == 1 and cpu_leg is not None:                 # (no path above should leave it pending)
         res["cpu_baseline"] = cpu_leg()
-    if world > 1 and not args.no_train and args.cameras == 1 and not args.cfg5:
+    if args.full and world > 1 and not args.no_train and args.cameras == 1 and not args.cfg5:
         # every rank takes part (collectives in the backward); after the timed render, outside it
         flat_t = {k: v.reshape(n_rays, -1) for k, v in batch.items() if k != "rand_vec"}
         ddp_res = ddp_train_step(device, flat_t, world, rank)

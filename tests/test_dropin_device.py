@@ -1,8 +1,8 @@
 """The drop-in overlay's names on a device: the body of the reference's training loop (train.py:142-224) and its
 render call (train.py:330) executed through `internal.models` / `internal.train_utils` AS THE OVERLAY RESOLVES THEM
 (PYTHONPATH=<repo>/ucnerf_amd/compat/dropin:<repo>, sitecustomize's meta-path finder), under `accelerate.Accelerator` like the
-reference (train.py:44,95,165,221).  tests/test_dropin_reference.py runs the reference's own scripts up to `Model(config=...)` in the
-authoring container; the GPU box has no reference tree, so the caller's `internal/` package is the stand-in under
+reference (train.py:44,95,165,221).  tools/dropin_harness.py runs the reference's own scripts up to `Model(config=...)` where a
+checkout of the reference exists; this test needs none, so the caller's `internal/` package is the stand-in under
 tests/stubs/upstream_internal_standin/ (three files whose presence the overlay checks; its train_utils carries a function the overlay
 must replace and one it must keep)."""
 import json

@@ -1,58 +1,10 @@
-"""SURVEY 8 row b1, literally: the reference's entry scripts, UNCHANGED, with only PYTHONPATH changed, construct this
-repo's Model under configs/waymo.gin's bindings.  Container-only: needs /root/reference (absent on the GPU box -> skipped);
-the harness and what it stubs are described in tests/dropin_harness.py."""
-import json
+"""The drop-in overlay's gin registration.  Running the reference's own entry scripts unchanged against the
+overlay needs a checkout of the reference, which is not part of this repository: tools/dropin_harness.py does that by hand."""
 import os
 import subprocess
 import sys
 
-import pytest
-
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/nerf"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference checkout is only present in the authoring container")
-
-
-def run_script(script):
-    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1",
-               PYTHONPATH=os.pathsep.join([os.path.join(REPO, "ucnerf_amd", "compat", "dropin"), REPO]))
-    p = subprocess.run([sys.executable, "-B", os.path.join(REPO, "tests", "dropin_harness.py"), script], cwd="/tmp", env=env,
-                       capture_output=True, text=True, timeout=600)
-    lines = [l for l in p.stdout.splitlines() if l.startswith("DROPIN_REPORT ")]
-    assert p.returncode == 0 and lines, p.stdout[-3000:] + p.stderr[-3000:]
-    return json.loads(lines[-1][len("DROPIN_REPORT "):])
-
-
-@pytest.mark.parametrize("script", ["train.py", "render.py", "eval.py", "extract.py", "tsdf.py"])
-def test_reference_script_constructs_this_repos_model_with_only_pythonpath_changed(script):
-    r = run_script(script)
-    dropin = os.path.join(REPO, "ucnerf_amd", "compat", "dropin", "internal")
-    # `from internal import models / train_utils` (train.py:17-18) resolved to the overlay; everything else to the reference
-    assert r["models_file"] == os.path.join(dropin, "models.py") and r["train_utils_file"] == os.path.join(dropin, "train_utils.py")
-    assert r["stepfun_file"].startswith(REF) and r["configs_file"].startswith(REF)
-    assert r["model_class"] == "ucnerf_amd.internal.models.Model"
-    assert r["model_is_ours"] and r["nerf_is_ours"] and r["prop_is_ours"] and r["render_image_is_ours"]
-    # configs/waymo.gin:10-20 reached the classes through gin (the reference's own Config object carries waymo.gin:1-8)
-    b = r["bound"]
-    assert (b["num_levels"], b["num_prop_samples"], b["num_nerf_samples"], b["opaque_background"]) == (2, 128, 32, False)
-    assert b["prop_disable_rgb"] is True and b["prop_disable_density_normals"] is True
-    assert b["nerf_disable_density_normals"] is True and b["nerf_disable_rgb"] is False and b["nerf_max_deg_point"] == 16
-    # a command-line --gin_bindings entry (NerfMLP.grid_log2_hashmap_size = 12): L = 10 levels of <= 4096 rows each
-    assert b["nerf_log2_hashmap"] == 12 and b["nerf_table_rows"] == 10 * 4096
-    c = r["config"]
-    assert c["type"] == "internal.configs.Config" and (c["near"], c["far"], c["batch_size"]) == (0.0, 8.0, 15000)
-    assert c["model_sky"] and c["brightness_correction"] and r["has_sky"] and r["has_brightness"]     # scripts/train_waymo.sh:11-12
-    # checkpoint layout = the reference's
-    keys = set(r["state_dict_keys"])
-    for k in ("nerf_mlp.encoder.embeddings", "nerf_mlp.density_layer.0.weight", "nerf_mlp.lin_second_stage_1.weight",
-              "nerf_mlp.rgb_layer.bias", "prop_mlp_0.encoder.embeddings", "prop_mlp_0.density_layer.2.weight",
-              "skynerf.pts_linears.7.weight", "skynerf.views_linears.0.weight", "skynerf.rgb_linear.bias",
-              "brightness_corr.latent_code", "brightness_corr.sky_latent_code", "brightness_corr.brightness_MLP.output_linear.weight"):
-        assert k in keys, k
-    assert not any(k.startswith("prop_mlp_1") for k in keys)
-    # the training step's helpers: hot-path losses / optimiser from this repo, the rest of train_utils from the reference
-    assert r["losses_are_ours"] and r["upstream_helpers_present"]
-    assert r["optimizer"] == "ucnerf_amd.internal.train_utils.FusedAdam" and abs(r["lr0"] - 0.01 * 1e-8) < 1e-12
 
 
 def test_models_register_with_gin_when_gin_is_importable():

@@ -291,7 +291,7 @@ def test_bench_two_ranks_flow_on_one_gpu():
     env = dict(os.environ, UCN_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     # the driver's N = 1 command form with N = 2: plain `python bench.py --gpus 2`, NO launcher -- bench.py must start the ranks itself
-    p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1"],
+    p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=repo)
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert p.returncode == 0 and len(lines) == 1, p.stdout[-2000:] + p.stderr[-3000:]

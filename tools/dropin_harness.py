@@ -1,16 +1,16 @@
-"""Container-only harness (needs /root/reference): runs the reference's OWN entry scripts' construction path with only
+"""Manual check (needs a checkout of the reference): runs the reference's OWN entry scripts' construction path with only
 PYTHONPATH changed -- `PYTHONPATH=<repo>/ucnerf_amd/compat/dropin:<repo>` -- and reports which classes they got.
 
-    python -B tests/dropin_harness.py train.py|render.py|eval.py
+    PYTHONPATH=<repo>/ucnerf_amd/compat/dropin:<repo> python -B tools/dropin_harness.py <reference>/nerf train.py|render.py|eval.py|extract.py|tsdf.py
 
-The script is executed unmodified from /root/reference/nerf (runpy, working directory and sys.path[0] as `python train.py`
+The script is executed unmodified from the reference's nerf/ directory (runpy, working directory and sys.path[0] as `python train.py`
 sets them); its `main()` runs from `configs.load_config()` (gin files + bindings from the command-line flags) through
 `accelerate.Accelerator()` to `models.Model(config=config)`; the harness records the instance the script built and stops at the next call
 (`train_utils.create_optimizer` / `datasets.load_dataset`: datasets need the Waymo files).  Third-party packages the image lacks are stubbed HERE, in
 the harness (test infrastructure): gin by tests/stubs/mini_gin.py (functional: bindings are parsed and injected), absl
 flags / app, cv2, lpips, skimage, rawpy, nuscenes, pyquaternion, pycolmap, tensorboardX, mediapy, imageio, trimesh,
 pymeshlab, torch_scatter.
-Nothing under /root/reference is written (bytecode off, exp_name points at a temp directory)."""
+Nothing in the reference checkout is written (bytecode off, exp_name points at a temp directory)."""
 import json
 import os
 import runpy
@@ -18,8 +18,8 @@ import sys
 import tempfile
 import types
 
-REF = '/root/reference/nerf'
-HERE = os.path.dirname(os.path.abspath(__file__))
+REF = None
+TESTS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests')
 sys.dont_write_bytecode = True
 
 
@@ -34,7 +34,7 @@ def _mod(name, **attrs):
 
 def install_stubs():
     import accelerate  # noqa: F401  (the real one; it probes optional trackers by name while importing)
-    sys.path.insert(0, os.path.join(HERE, 'stubs'))
+    sys.path.insert(0, os.path.join(TESTS, 'stubs'))
     import mini_gin
     sys.modules['gin'] = mini_gin
     flags = _mod('absl.flags', FLAGS=types.SimpleNamespace(gin_configs=None, gin_bindings=None),
@@ -63,7 +63,8 @@ class Grabbed(Exception):
 
 
 def main():
-    script = sys.argv[1]
+    global REF
+    REF, script = os.path.abspath(sys.argv[1]), sys.argv[2]
     tmp = tempfile.mkdtemp(prefix='ucn_dropin_')
     install_stubs()
     os.chdir(REF)

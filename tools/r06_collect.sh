@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd $R; O=gpurun_out/r06c; mkdir -p $O
 python -m pytest tests -m gpu -q 2>&1 | tail -15 > $O/gpu_suite.txt
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 bash tools/pmc_passes.sh r06c_pmc > $O/pmc_passes.log 2>&1
 PMC_GLOB="gpurun_out/r06c_pmc/pmc_*/p_counter_collection.csv" python tools/pmc_table.py > $O/pmc_table.txt 2>&1
 python tools/traffic_json.py r06c_pmc > $O/traffic.log 2>&1; cp gpurun_out/r06c_pmc/traffic.json $O/traffic.json
