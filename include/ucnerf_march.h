@@ -190,8 +190,9 @@ int ucn_march_features_backward(const ucn_field_t *f, const float *sdist, const 
                                                    cannot compact its work (several times slower)*/,
                                 ucn_stream_t stream);
 uint64_t ucn_march_features_backward_ws_floats(const ucn_field_t *f, uint32_t N, uint32_t S);
-/* ABI 26: 1 if that call (levels_per_block = 0, with its workspace) runs the compacted row-block kernel -- the only route that accepts
- * sample_major = 4; 0 where it would fall back (more than 512 row blocks per level, >= 2^29 samples). */
+/* ABI 26: 1 if that call (levels_per_block = 0, with its workspace) runs the compacted row-block kernel under float AND under
+ * fixed-point rows -- the only route that accepts sample_major = 4; 0 where it would fall back (more than 512 row blocks in a level,
+ * >= 2^29 samples, or a level of more than 32 row blocks with >= 2^24 samples) and for N * S = 0. */
 int ucn_march_features_backward_row_blocks(const ucn_field_t *f, uint32_t N, uint32_t S);
 
 /* Introspection of the fused featurisation's geometry stage (the parity tests of SURVEY 8 rows a5 / a6; not on the

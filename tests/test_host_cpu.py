@@ -348,6 +348,41 @@ def test_host_offsets_cache_lives_on_the_tensor():
     assert list(_backend.host_offsets(a)) == [0, 32, 64]
 
 
+def test_row_block_route_of_the_table_gradient_is_decided_on_the_host():
+    """ucn_march_features_backward_row_blocks: 1 where ucn_march_features_backward(levels_per_block = 0, with a workspace) takes the
+    compacted row-block kernel under both row types -- the only route that reads a layout-4 gradient --, 0 where it falls back.
+    Host-only (the mask plan; the embeddings pointer is never read)."""
+    import bench
+    from ucnerf_amd import _lib
+    from ucnerf_amd.internal import models
+    lib = _lib.load()
+    table = torch.zeros(8)
+
+    def row_blocks(offsets, sizes, C, base, log2_scale, N, S):
+        offsets, sizes = np.ascontiguousarray(offsets, dtype=np.int32), np.ascontiguousarray(sizes, dtype=np.int32)
+        d = _lib.UcnField()
+        d.embeddings = table.data_ptr()
+        d.offsets_host, d.grid_sizes_host = offsets.ctypes.data, sizes.ctypes.data
+        d.num_levels, d.level_dim, d.base_resolution, d.log2_per_level_scale = len(sizes), C, base, log2_scale
+        return lib.ucn_march_features_backward_row_blocks(ctypes.byref(d), N, S)
+
+    def grid(enc, N, S):
+        return row_blocks(enc._offsets_np, enc._sizes_np, enc.level_dim, enc.base_resolution, float(np.log2(enc.per_level_scale)), N, S)
+
+    with models.bindings(NerfMLP=dict(grid_disired_resolution=524288, grid_level_dim=2, grid_log2_hashmap_size=19)):
+        nerf = models.NerfMLP().encoder                                 # BASELINE configs[2]'s NeRF level: C = 2, T = 2^19
+    waymo = models.NerfMLP().encoder                                    # the reference's waymo.gin: L = 10, C = 4, T = 2^21
+    assert int(waymo._offsets_np[-1] - waymo._offsets_np[-2]) == 256 * 8192             # 256 row blocks of 8192 rows
+    assert grid(nerf, 8192, bench.S_NERF) == 1
+    assert grid(nerf, (1 << 29) // bench.S_NERF - 1, bench.S_NERF) == 1
+    assert grid(nerf, (1 << 29) // bench.S_NERF, bench.S_NERF) == 0                   # N * S >= 2^29: the sample no longer fits an item
+    assert grid(waymo, 8192, 32) == 1
+    assert grid(waymo, (1 << 24) // 32, 32) == 0                                         # > 32 blocks per level and N * S >= 2^24
+    assert row_blocks([0, 1 << 23], [257], 4, 256, 0.0, 8192, 32) == 0                  # 1024 row blocks of 8192 rows: > 512
+    assert row_blocks([0, 512 * 8192], [257], 4, 256, 0.0, 8192, 32) == 1               # 512: the most a level may have
+    assert grid(nerf, 0, bench.S_NERF) == 0
+
+
 def test_fields_survive_deepcopy_and_pickle():
     """cached C descriptors (ctypes structs with raw pointers) must not travel with copy / pickle."""
     import copy

@@ -223,13 +223,7 @@ __device__ __forceinline__ void level_accumulate_shared(const UcnLevel &lv, cons
         uint32_t row;
         if constexpr (POW2) row = idx & lv.mask;
         else row = idx < lv.rows ? idx : idx % lv.rows;
-#ifdef UCN_EXP_NO_COARSE_LOADS            // experiment build (r04): the coarse levels WITHOUT their table reads -- the ceiling of any LDS staging
-        (void)row;
-#pragma unroll
-        for (uint32_t c = 0; c < C; c++) v[k][c] = __builtin_bit_cast(float, 0x3f000000u + k * 977u + c);
-#else
         load_row<C, TT>(tab, row, v[k]);
-#endif
     }
 #pragma unroll
     for (uint32_t j = 0; j < 6; j++) {
@@ -307,14 +301,12 @@ __device__ __forceinline__ void level_accumulate_pairs(const UcnLevel &lv, const
 //   swap(a, b) -> {a.lo, b.lo}, {a.hi, b.hi}.  4.5 line requests per point instead of 6 (pair fetch) or 8, no divergent branch.
 // Points outside the unit cube fetch (masked, hence valid) dummy rows and are skipped at the accumulation: same values, same
 // fmaf order as level_accumulate.  Needs every lane of the wave active (the caller checks).
+constexpr uint32_t kLanePairDepth = 1;                              // points whose 8 loads are in flight together (2 / 3 / 6 measured: DESIGN)
 template <bool HASHED, typename TT>
 __device__ __forceinline__ void level_accumulate_lanepairs(const UcnLevel &lv, const TT *__restrict__ tab,
                                                            const float (&u)[6][3], const float (&rs)[6], float (&acc)[2]) {
     acc[0] = acc[1] = 0.0f;
-#ifndef UCN_LANEPAIR_DEPTH
-#define UCN_LANEPAIR_DEPTH 1
-#endif
-    constexpr uint32_t DEPTH = UCN_LANEPAIR_DEPTH;                  // points whose 8 loads are in flight together (experiment knob)
+    constexpr uint32_t DEPTH = kLanePairDepth;
 #pragma unroll
     for (uint32_t j0 = 0; j0 < 6; j0 += DEPTH) {
         float fx[DEPTH], fy[DEPTH], fz[DEPTH];
@@ -628,24 +620,19 @@ __device__ __forceinline__ void level_scatter_block(const UcnLevel &lv, A *__res
     }
 }
 
-#ifndef UCN_SHARED_CELL_MAX_RES
-#define UCN_SHARED_CELL_MAX_RES 64
-#endif
-#ifndef UCN_LANEPAIR_MIN_RES
-#define UCN_LANEPAIR_MIN_RES 2048u                                  // levels finer than this take the lane-paired fetch when a wave's rays are
-//                                                                     neighbouring pixels (rendering: on the middle levels the lanes share lines anyway
-//                                                                     and the three swaps per corner pair cost more than they save -- per-level times in
-//                                                                     profiles/r04/level_times_*.txt); UCN_RAYS_INCOHERENT (random training rays, no
-//                                                                     sharing on any hashed level) lowers it to kSharedCellMaxRes
-#endif
-constexpr uint32_t kSharedCellMaxRes = UCN_SHARED_CELL_MAX_RES;     // dense levels up to this resolution use level_accumulate_shared
+constexpr uint32_t kSharedCellMaxRes = 64;                          // dense levels up to this resolution use level_accumulate_shared
+// levels finer than this take the lane-paired fetch when a wave's rays are neighbouring pixels (rendering: on the middle levels the
+// lanes share lines anyway and the three swaps per corner pair cost more than they save -- per-level times in
+// profiles/r04/level_times_*.txt); UCN_RAYS_INCOHERENT (random training rays, no sharing on any hashed level) lowers it to
+// kSharedCellMaxRes
+constexpr uint32_t kLanePairMinRes = 2048u;
 
 // layout: 0 = [L][B][C] (b as given), 1 = [B][L*C]
 template <uint32_t C, typename TT>
 __device__ __forceinline__ void featurise(const UcnLevels &lvls, const TT *__restrict__ table, uint32_t lvl0,
                                           uint32_t lvl1, const float (&u)[6][3], const float (&rs)[6], uint32_t G,
                                           size_t B, size_t b, float *__restrict__ out, bool sample_major, bool out_bf16 = false,
-                                          bool full_wave = false, uint32_t lp_min_res = UCN_LANEPAIR_MIN_RES) {
+                                          bool full_wave = false, uint32_t lp_min_res = kLanePairMinRes) {
     const uint32_t F_out = lvls.L * C;
     for (uint32_t lvl = lvl0; lvl < lvl1; lvl++) {
         const UcnLevel lv = lvls.lv[lvl];
@@ -657,11 +644,8 @@ __device__ __forceinline__ void featurise(const UcnLevels &lvls, const TT *__res
             else level_accumulate_shared<C, true, false>(lv, tab, u, rs, acc);
         } else if (lv.hashed) {
             if constexpr (C == 2) {
-#ifndef UCN_NO_LANEPAIRS
                 if (lv.mask && G == 6 && full_wave && lv.resolution > lp_min_res) level_accumulate_lanepairs<true, TT>(lv, tab, u, rs, acc);
-                else
-#endif
-                if (lv.mask && lv.resolution > 2048u && G == 6) level_accumulate_pairs(lv, tab, u, rs, acc);
+                else if (lv.mask && lv.resolution > 2048u && G == 6) level_accumulate_pairs(lv, tab, u, rs, acc);
                 else if (lv.mask) level_accumulate<C, true, true>(lv, tab, u, rs, G, acc);
                 else level_accumulate<C, true, false>(lv, tab, u, rs, G, acc);
             } else {
@@ -672,7 +656,6 @@ __device__ __forceinline__ void featurise(const UcnLevels &lvls, const TT *__res
             if (lv.mask) level_accumulate_shared<C, false, true>(lv, tab, u, rs, acc);
             else level_accumulate_shared<C, false, false>(lv, tab, u, rs, acc);
         } else {
-#ifndef UCN_NO_LANEPAIRS
             if constexpr (C == 2) {
                 if (lv.mask && G == 6 && full_wave && lv.stride[0] == 1u && lv.resolution > lp_min_res) {
                     level_accumulate_lanepairs<false, TT>(lv, tab, u, rs, acc);
@@ -680,9 +663,7 @@ __device__ __forceinline__ void featurise(const UcnLevels &lvls, const TT *__res
                     if (lv.mask) level_accumulate<C, false, true>(lv, tab, u, rs, G, acc);
                     else level_accumulate<C, false, false>(lv, tab, u, rs, G, acc);
                 }
-            } else
-#endif
-            {
+            } else {
                 if (lv.mask) level_accumulate<C, false, true>(lv, tab, u, rs, G, acc);
                 else level_accumulate<C, false, false>(lv, tab, u, rs, G, acc);
             }
@@ -903,7 +884,7 @@ __global__ __launch_bounds__(TPB) void k_march_features(UcnLevels lvls, const TT
     cast_sample(in, hx, std_scale, ray, s, S, u, rs, csum, tsum);
     const uint32_t lvl0 = grp.lo[blockIdx.y], lvl1 = grp.lo[blockIdx.y + 1];
     const bool full_wave = __ballot(true) == ~0ull;                  // the lane-paired fetch trades rows between lanes i and i + 32
-    const uint32_t lp_min = (layout & 0x20) ? kSharedCellMaxRes : UCN_LANEPAIR_MIN_RES;     // 0x20: UCN_RAYS_INCOHERENT (private bit)
+    const uint32_t lp_min = (layout & 0x20) ? kSharedCellMaxRes : kLanePairMinRes;     // 0x20: UCN_RAYS_INCOHERENT (private bit)
     if constexpr (sizeof(TT) == 2) featurise<C, TT>(lvls, table, lvl0, lvl1, u, rs, 6, B, b, features, (layout & 3) == 1, (layout & 0x10) != 0, full_wave, lp_min);
     else featurise<C, TT>(lvls, table, lvl0, lvl1, u, rs, 6, B, b, features, (layout & 3) == 1, false, full_wave, lp_min);
     if (blockIdx.y == 0) {
@@ -974,36 +955,25 @@ static GradStrides grad_strides(int layout, size_t B, uint32_t L, uint32_t C) {
     return {B * C, C, 1};
 }
 
-#ifndef UCN_KSCAN
-#define UCN_KSCAN 4
-#endif
-constexpr uint32_t kScan = UCN_KSCAN;                          // samples per thread and scan step (8 measured: see DESIGN)
-#ifndef UCN_MASKS_MIN_BLOCKS
-#define UCN_MASKS_MIN_BLOCKS 1                           // experiment knob (r06): workgroups per CU the mask pass is compiled for.  8 = 64 registers (4 spilled), 8 waves per SIMD instead of 5 at 95: the autocast step's pass 0.419 -> 0.374 ms, but the fp32 step (row-major gradient copied and divided here) 14.52 -> 14.70 ms; 6 = 67 registers: 0.399 ms.  Not taken
-#endif
-#ifndef UCN_BWD_BYTE_MASKS_DEFAULT
-#define UCN_BWD_BYTE_MASKS_DEFAULT 1
-#endif
+constexpr uint32_t kScan = 4;                                  // samples per thread and scan step (8 measured: see DESIGN)
 constexpr uint32_t kMaxMaskWords = 16;                  // sample-item levels: up to 512 row blocks (16 KiB of LDS in the mask pass)
 struct MaskPlan {
     uint16_t plane[UCN_MAX_LEVELS];
     uint8_t coarse[UCN_MAX_LEVELS];
     uint32_t n_planes, shift;
     uint16_t split[UCN_MAX_LEVELS];        // workgroups per row block (cut along the samples): ~128 per level, 256 for the last
-    uint32_t skip_fine;                    // 1: the fine levels are taken by the item-list kernels (k_bwd_list), not by bwd_cmp
     uint8_t order[UCN_MAX_LEVELS];         // levels in the order their workgroups are dispatched: longest workgroups first
-    uint8_t fine_kind[UCN_MAX_LEVELS];     // point-item levels: 0 = ballot-ordered items + corner walk, 1 = lane-ordered items + corner walk, 2 = lane-ordered + (y, z) combinations, 3 = 2 on byte planes (cmp_block_bytes)
+    uint8_t fine_kind[UCN_MAX_LEVELS];     // point-item levels: 0 = ballot-ordered items + corner walk, 2 = lane-ordered items + (y, z) combinations, 3 = 2 on byte planes (cmp_block_bytes)
 };
 __host__ __device__ __forceinline__ uint32_t bwd_sample_split(uint32_t blocks_in_level, uint32_t target = 128u) {
     return blocks_in_level >= target ? 1u : target / blocks_in_level;     // ~`target` workgroups per level (default 128)
 }
-static bool make_mask_plan(const UcnLevels &lv, uint32_t rpb, size_t B, MaskPlan *mp, bool fixed_rows = false) {
+static bool make_mask_plan(const UcnLevels &lv, uint32_t rpb, size_t B, MaskPlan *mp, bool fixed_rows) {
     uint32_t shift = 0;
     while ((1u << shift) < rpb) shift++;
     if ((1u << shift) != rpb) return false;
     mp->shift = shift;
     mp->n_planes = 0;
-    mp->skip_fine = 0u;
     for (uint32_t l = 0; l < lv.L; l++) {
         const uint32_t nb_l = (lv.lv[l].rows + rpb - 1) / rpb;
         if (nb_l > kMaxMaskWords * 32u) return false;                     // (> 512 blocks, e.g. 2^23 rows of C = 4: the atomic fallback)
@@ -1011,52 +981,37 @@ static bool make_mask_plan(const UcnLevels &lv, uint32_t rpb, size_t B, MaskPlan
         // resolution 512, walking consecutive samples in one lane up to 64
         // r06, FIXED-POINT rows (the autocast step): a row update is one fire-and-forget ds_add_u64 there, so run merging buys nothing
         // and the ~8 row blocks a SAMPLE of the hashed levels 84 ... 446 touches each redo all of its 48 corners; as point items on byte
-        // planes those levels cost 44-47 instead of 45-82 ms-CU each (tools/bwd_balance.py under UCN_TOOL_FX=1, whole call 3.54 ->
-        // 3.20 ms; profiles/r06/bwd_coarse_res_fx.txt).  With float rows the same change LOSES (3.71 -> 5.3 ms: compare-and-swap
-        // collisions; bwd_coarse_res_float.txt), so the threshold follows the row type.
-        static const int coarse_res_env = getenv("UCN_BWD_COARSE_RES") ? atoi(getenv("UCN_BWD_COARSE_RES")) : -1;                 // experiment knob
-        const uint32_t coarse_res = coarse_res_env >= 0 ? (uint32_t)coarse_res_env : (fixed_rows ? 64u : 512u);
+        // planes those levels cost 44-47 instead of 45-82 ms-CU each (whole call 3.54 -> 3.20 ms; profiles/r06/bwd_coarse_res_fx.txt).
+        // With float rows the same change LOSES (3.71 -> 5.3 ms: compare-and-swap collisions; bwd_coarse_res_float.txt), so the
+        // threshold follows the row type.
+        const uint32_t coarse_res = fixed_rows ? 64u : 512u;
         mp->coarse[l] = lv.lv[l].resolution <= coarse_res ? 1 : 0;
-        // (experiment knob, r06: under fixed-point rows the plain sample item is cheaper than the walk on the dense levels too -- 17.1 / 19.4 /
-        // 39.1 -> 12.7 / 16.3 / 32.3 ms-CU, call 3.205 -> 3.164 ms, step -0.05 ... -0.1 ms -- but merging runs ACROSS six samples also means six
-        // times fewer ROUNDED addends on exactly the rows that collect the most samples: 2.4 x the fixed-point noise there (a fuzz case of
-        // 640 000 random-sign gradients went from < 1e-3 to 1.24e-3 of the largest entry) for 1 % of the step.  Not taken: 64 for both row types)
-        static const uint32_t runs_res = getenv("UCN_BWD_RUNS_RES") ? (uint32_t)atoi(getenv("UCN_BWD_RUNS_RES")) : 64u;
-        if (mp->coarse[l] && !lv.lv[l].hashed && lv.lv[l].resolution <= runs_res) mp->coarse[l] = 2;
+        // (r06: under fixed-point rows the plain sample item is cheaper than the walk on the dense levels too -- call 3.205 -> 3.164 ms --
+        // but merging runs ACROSS six samples also means six times fewer ROUNDED addends on exactly the rows that collect the most
+        // samples: 2.4 x the fixed-point noise there for 1 % of the step.  Not taken: 64 for both row types)
+        if (mp->coarse[l] && !lv.lv[l].hashed && lv.lv[l].resolution <= 64u) mp->coarse[l] = 2;
         // More than 32 row blocks per level (the reference's own waymo.gin grid: T = 2^21 rows of C = 4 -> 256 blocks of 8192 rows):
         // the per-point masks of the point-item shapes would need 6 bits x 256 blocks per sample and level, so such a level goes by
         // SAMPLE items as well -- one bit per (sample, block) in nb / 32 mask words -- with the unmerged per-point scatter (a point's
         // corners lie in ~4.5 of the 256 blocks: the `any corner in my block` test drops most points before weights and erf).
         // Before r03 these configurations fell back to the global-atomic kernel: 83.6 of the 88.5 ms of a waymo.gin training step.
         if (nb_l > 32u && mp->coarse[l] != 2) mp->coarse[l] = 3;         // (the run-merging dense levels keep their shape, with nb / 32 mask words)
-        // experiment knob (r04): the hashed sample-item levels (resolution 128 ... 512) through the pair-item shape as well
-        static const bool wide_mid = getenv("UCN_BWD_WIDE_MID") && atoi(getenv("UCN_BWD_WIDE_MID")) != 0;
-        if (wide_mid && mp->coarse[l] == 1 && lv.lv[l].hashed && nb_l == 32u) mp->coarse[l] = 3;
-        // Point-item levels, three shapes (workgroup clocks per level, tools/bwd_balance.py, ms-CU per level of the benchmark grid):
+        // Point-item levels (<= 32 row blocks), three shapes (ms-CU per level of the benchmark grid):
         //   0: items appended point by point (six ballots per step), all 8 corners walked          res 1024: 75, 2048: 62, finer: 60-62, strided: 78
-        //   1: items appended lane by lane (popcount + one DPP prefix sum per step: the scan was a third of a fine level)   1024: 120 (!), 2048: 78, finer: 51-55
-        //   2: 1 + the corners taken by (y, z) combinations (point_scatter_combos)                   1024: 120, 2048: 78, finer: 51-55 (shape 1 alone: 58-60), strided: 60
+        //   2: items appended lane by lane (popcount + one DPP prefix sum per step), the corners taken by (y, z) combinations
+        //      (point_scatter_combos)                                                                 1024: 120, 2048: 78, finer: 51-55, strided: 60
+        //   3 (r06): shape 2 on BYTE PLANES -- per row block one byte per sample (bit j = multisample j has a corner in the block), so
+        //      that a scanning lane reads FOUR samples of ITS block in one dword (popcount 3.4 on average) where the nibble planes
+        //      give it one sample of four blocks (0.84 hits).  Same number of planes; needs B % 4 == 0 (a quad of samples per dword).
         // Lane order puts the six points of a sample next to each other in a batch: where they still share lattice cells
-        // (resolution <= 2048 on these rays) their compare-and-swaps collide and fall back to ds_add_f32.
+        // (resolution <= 2048 on these rays) their compare-and-swaps collide and fall back to ds_add_f32 -- so float rows keep shape 0
+        // there; fixed-point rows (fire-and-forget adds, nothing to collide) take byte planes on every point-item level.
+        // (Removed after measurement, numbers in profiles/: shape 1 = lane order + corner walk, shape 4 = byte planes + corner walk.)
         mp->fine_kind[l] = 0;
-        if (!mp->coarse[l]) mp->fine_kind[l] = (!lv.lv[l].hashed || lv.lv[l].resolution >= 4096u) ? 2 : 0;
-        static const int force_kind = getenv("UCN_BWD_FINE_KIND") ? atoi(getenv("UCN_BWD_FINE_KIND")) : -1;      // experiment knob
-        if (!mp->coarse[l] && force_kind >= 0 && force_kind <= 2) mp->fine_kind[l] = (uint8_t)force_kind;
-        // 3 (r06, VERDICT r05 item 2 b): shape 2 with BYTE PLANES -- per row block one byte per sample (bit j = multisample j has a
-        // corner in the block), so that a scanning lane reads FOUR samples of ITS block in one dword (popcount 3.4 on average)
-        // where the nibble planes above give it one sample of four blocks (0.84 hits): one load, one popcount and one DPP prefix
-        // sum per 4096-sample unit instead of four.  Same number of planes.  UCN_BWD_BYTE_MASKS=0: off; =2: every point-item level
-        // (the lane order of its items makes the compare-and-swaps of resolution 1024 / 2048 collide, as with shape 1).
-        static const int byte_masks_env = getenv("UCN_BWD_BYTE_MASKS") ? atoi(getenv("UCN_BWD_BYTE_MASKS")) : -1;
-        const int byte_masks = byte_masks_env >= 0 ? byte_masks_env : (fixed_rows ? 2 : UCN_BWD_BYTE_MASKS_DEFAULT);   // fixed-point rows: every point-item level (no compare-and-swap to collide)
-        if (!mp->coarse[l] && nb_l <= 32u && B % 4u == 0u && kScan == 4u &&
-            ((byte_masks == 1 && mp->fine_kind[l] == 2) || byte_masks == 2 || (byte_masks == 3 && mp->fine_kind[l] == 2)))
-            mp->fine_kind[l] = 3;
-        // 4 (=3 only, experiment): the byte-plane scan with the CORNER WALK of shape 0 for the levels whose points still share cells
-        // (resolution 1024 / 2048) -- only where the row updates are fire-and-forget fixed-point adds: with compare-and-swap rows the
-        // lane order of the items makes neighbouring lanes fight for one row
-        else if (!mp->coarse[l] && nb_l <= 32u && B % 4u == 0u && kScan == 4u && byte_masks == 3 && fixed_rows && mp->fine_kind[l] == 0)
-            mp->fine_kind[l] = 4;
+        if (!mp->coarse[l]) {
+            const uint8_t kind0 = (!lv.lv[l].hashed || lv.lv[l].resolution >= 4096u) ? 2 : 0;
+            mp->fine_kind[l] = (B % 4u == 0u && (fixed_rows || kind0 == 2)) ? 3 : kind0;
+        }
         mp->plane[l] = (uint16_t)mp->n_planes;
         if (mp->coarse[l] == 3) {
             // bit planes: [block][ceil(B / 64)] 64-bit words (one bit per sample) = nb x 2 x ceil(B / 64) 32-bit words, in units of B
@@ -1067,12 +1022,12 @@ static bool make_mask_plan(const UcnLevels &lv, uint32_t rpb, size_t B, MaskPlan
         }
     }
     // Dispatch order = longest workgroups first, so that the chip drains on short ones (workgroup clocks of the benchmark
-    // grid, tools/bwd_balance.py: in level order the last 1.3 ms of a 4.26 ms kernel ran at 50-85 % occupancy -- the two
-    // finest levels started at 3.1 / 3.4 ms -- where the sum of the workgroup times is 3.70 ms per CU).  Classes by what was
-    // measured per workgroup: unhashed levels of more than two row blocks load their blocks unevenly (the strided fine levels
-    // of the uint32-wrap quirk: 150 ... 1010 us; the dense 65^3 level: 45 ... 890 us) and go first; then the hashed
-    // sample-item levels, finest first (690 / 510 / 420 us); then the hashed point-item levels, coarsest first (600 ... 460 us);
-    // the small dense levels (140 us) fill the tail.
+    // grid: in level order the last 1.3 ms of a 4.26 ms kernel ran at 50-85 % occupancy -- the two finest levels started at
+    // 3.1 / 3.4 ms -- where the sum of the workgroup times is 3.70 ms per CU).  Classes by what was measured per workgroup:
+    // unhashed levels of more than two row blocks load their blocks unevenly (the strided fine levels of the uint32-wrap quirk:
+    // 150 ... 1010 us; the dense 65^3 level: 45 ... 890 us) and go first; then the hashed sample-item levels, finest first
+    // (690 / 510 / 420 us); then the hashed point-item levels, coarsest first (600 ... 460 us); the small dense levels (140 us)
+    // fill the tail.
     uint32_t key[UCN_MAX_LEVELS];
     for (uint32_t l = 0; l < lv.L; l++) {
         const uint32_t nb = (lv.lv[l].rows + rpb - 1) / rpb;
@@ -1089,22 +1044,18 @@ static bool make_mask_plan(const UcnLevels &lv, uint32_t rpb, size_t B, MaskPlan
         for (uint32_t j = i; j > 0 && key[mp->order[j]] > key[mp->order[j - 1]]; j--) {
             const uint8_t t = mp->order[j]; mp->order[j] = mp->order[j - 1]; mp->order[j - 1] = t;
         }
-    if (getenv("UCN_BWD_LEVEL_ORDER"))                                     // experiment knob: dispatch in level order
-        for (uint32_t l = 0; l < lv.L; l++) mp->order[l] = (uint8_t)l;
     // ~128 workgroups per level (flat from 128 up, measured); the LAST long level of the order is cut twice as fine: the
-    // chip drains on its workgroups (the small dense levels behind it are 35 ms-CU in all), and half-length ones halve that
-    static const uint32_t wg_target = getenv("UCN_BWD_WGS") && atoi(getenv("UCN_BWD_WGS")) > 0 ? (uint32_t)atoi(getenv("UCN_BWD_WGS")) : 128u;
-    static const bool fine_tail = !getenv("UCN_BWD_NO_FINE_TAIL");       // experiment knobs, both
+    // chip drains on its workgroups (the small dense levels behind it are 35 ms-CU in all), and half-length ones halve that.
+    // The unevenly loaded levels are cut twice as fine as well: their hottest block sets the longest workgroup of the call
+    // (waymo.gin's proposal grid, 1 M samples: one 4.7 ms workgroup of the dense 65^3 level against 2.4 ms-CU of work per CU;
+    // 1 / 2 / 4 / 8 measured: 2)
     int last_long = -1;
     for (uint32_t i = 0; i < lv.L; i++)
         if (key[mp->order[i]] >= 256u) last_long = (int)mp->order[i];
     for (uint32_t l = 0; l < lv.L; l++) {
         const uint32_t nb = (lv.lv[l].rows + rpb - 1) / rpb;
-        // ... and the unevenly loaded levels finer as well: their hottest block sets the longest workgroup of the call (waymo.gin's
-        // proposal grid, 1 M samples: one 4.7 ms workgroup of the dense 65^3 level against 2.4 ms-CU of work per CU)
-        static const uint32_t uneven_mult = getenv("UCN_BWD_UNEVEN_MULT") ? (uint32_t)atoi(getenv("UCN_BWD_UNEVEN_MULT")) : 2u;   // experiment knob (1 / 2 / 4 / 8 measured: 2)
-        const uint32_t mult = key[l] >= 3u * 256u ? (uneven_mult ? uneven_mult : 1u) : ((fine_tail && (int)l == last_long) ? 2u : 1u);
-        mp->split[l] = (uint16_t)bwd_sample_split(nb, mult * wg_target);
+        const uint32_t mult = (key[l] >= 3u * 256u || (int)l == last_long) ? 2u : 1u;
+        mp->split[l] = (uint16_t)bwd_sample_split(nb, mult * 128u);
     }
     return true;
 }
@@ -1131,7 +1082,7 @@ __device__ __forceinline__ uint32_t point_block_mask(const UcnLevel &lv, uint32_
 }
 
 // geometry planes + block masks of every sample, once per backward call
-__global__ __launch_bounds__(256, UCN_MASKS_MIN_BLOCKS) void k_cast_cache_masks(UcnLevels lvls, RayInputs in, HexPattern hx, float std_scale,
+__global__ __launch_bounds__(256, 1) void k_cast_cache_masks(UcnLevels lvls, RayInputs in, HexPattern hx, float std_scale,
                                                           uint32_t N, uint32_t S, MaskPlan plan,
                                                           const float *__restrict__ grad_features, GradStrides gs, uint32_t C,
                                                           float *__restrict__ geom, uint32_t *__restrict__ masks,
@@ -1165,12 +1116,7 @@ __global__ __launch_bounds__(256, UCN_MASKS_MIN_BLOCKS) void k_cast_cache_masks(
         const uint32_t nb_l = (lv.rows + (1u << plan.shift) - 1u) >> plan.shift;
         bool nz = false;
         float gmax = 0.0f;
-#ifdef UCN_EXP_MASKS_NO_GRAD                                   // timing-only build (results garbage): geometry + masks alone, i.e. what is left
-        nz = valid;                                            // of this pass if k_train_bwd's epilogue wrote the level-major gradient (VERDICT r05 item 2 c)
-        for (uint32_t c = 0; c < 0u; c++) {
-#else
         for (uint32_t c = 0; c < C; c++) {
-#endif
             const float g = grad_features[lvl * gs.level + bb * gs.sample + c * gs.chan];
             nz |= valid && g != 0.0f;
             gmax = fmaxf(gmax, valid ? fabsf(g) : 0.0f);
@@ -1181,11 +1127,7 @@ __global__ __launch_bounds__(256, UCN_MASKS_MIN_BLOCKS) void k_cast_cache_masks(
             if (valid && grad_level_major) grad_level_major[((size_t)lvl * B + b) * C + c] = g / 6.0f;
         }
         if (!grad_level_major) gmax *= 6.0f;                // layout 4: g arrived divided by 6 -- the bound is on the undivided gradient (6 addends of <= |g| / 6 x w)
-#ifndef UCN_EXP_MASKS_NO_GRAD
         if (l1_partial) {                                   // (workgroup-uniform; every wave of the block gets here: no early `continue` above)
-#else
-        if (false) {
-#endif
             const float wsum = wave_sum_dpp<float>(gmax);
             if ((threadIdx.x & 63u) == 0u) s_l1[lvl][threadIdx.x >> 6] = wsum;
         }
@@ -1250,7 +1192,7 @@ __global__ __launch_bounds__(256, UCN_MASKS_MIN_BLOCKS) void k_cast_cache_masks(
 #pragma unroll
             for (uint32_t j = 0; j < 6; j++) m[j] = 0u;
         }
-        if (plan.fine_kind[lvl] >= 3 && !plan.coarse[lvl]) {
+        if (plan.fine_kind[lvl] == 3) {
             // BYTE PLANES (cmp_block_bytes): plane p = B bytes, byte b = the six point bits of sample b for row block p.  A thread
             // spreads its masks into words of four block bytes (nibble x 0x00204081 puts bit i of a nibble at bit 8 i), the four
             // threads of a quad (samples 4 q ... 4 q + 3; B % 4 == 0, so a quad is in range or not as a whole) transpose 4 x 4 bytes
@@ -1377,9 +1319,6 @@ __device__ __forceinline__ void point_scatter_combos(const UcnLevel &lv, A *__re
     }
     const float damp = erf_pos(rsj * lv.inv_gs);
     const float gx = 1.0f - fx, gy = 1.0f - fy, gz = 1.0f - fz;
-#ifdef UCN_EXP_NO_UPDATE                                                            // experiment build: everything but the LDS updates
-    if (damp + gx + gy + gz != 12345.0f) pend &= (fx == 77.0f ? 15u : 0u);
-#endif
     while (pend) {
         const uint32_t c = (uint32_t)__builtin_ctz(pend);
         pend &= pend - 1u;
@@ -1517,7 +1456,7 @@ __device__ __forceinline__ void cmp_fetch(uint32_t item, bool valid, size_t B, c
     }
 }
 
-template <uint32_t C, bool HASHED, bool POW2, bool COARSE, bool RUNS, int FINE = 0, typename A = float>
+template <uint32_t C, bool HASHED, bool POW2, bool COARSE, bool RUNS, bool COMBOS = false, typename A = float>
 __device__ __forceinline__ void cmp_block(const UcnLevel &lv, A *__restrict__ s_acc, uint32_t *__restrict__ q, uint32_t blk,
                                           uint32_t row_lo, uint32_t nrows, uint32_t part, uint32_t split, size_t B,
                                           const uint32_t *__restrict__ mp, const float *__restrict__ gl,
@@ -1555,7 +1494,7 @@ __device__ __forceinline__ void cmp_block(const UcnLevel &lv, A *__restrict__ s_
 #pragma unroll
             for (uint32_t uu = 1; uu < kScan; uu++) m = u == uu ? cur[uu] : m;
             m >>= bit0;
-            if constexpr (COARSE || FINE == 0) {
+            if constexpr (!COMBOS) {
 #pragma unroll
                 for (uint32_t j = 0; j < P; j++) {
                     const bool act = (m >> (4u * j)) & 1u;
@@ -1623,22 +1562,19 @@ __device__ __forceinline__ void cmp_block(const UcnLevel &lv, A *__restrict__ s_
                 if (run.have) run_flush<C>(s_acc, row_lo, nrows, run, glast);   // (lean runs are closed by run_merge_sample: never open here)
             } else {
                 // two items per lane: both items' loads are in flight before the first scatter starts
-#ifdef UCN_EXP_SCAN_ONLY                                                    // experiment build: what the mask scan alone costs
-                if (!RUNS) { head += avail; continue; }
-#endif
                 const uint32_t i0 = q[(head + lane) & (kQueue - 1u)], i1 = q[(head + 64u + lane) & (kQueue - 1u)];
                 const bool v0 = lane < avail, v1 = lane + 64u < avail;
                 float u0[6][3], rs0[6], g0[C], u1[6][3], rs1[6], g1[C];
                 cmp_fetch<C, HASHED, POW2, COARSE>(i0, v0, B, gl, geom, u0, rs0, g0, gscale);
                 cmp_fetch<C, HASHED, POW2, COARSE>(i1, v1, B, gl, geom, u1, rs1, g1, gscale);
                 if (v0) {
-                    if constexpr (COARSE) level_scatter_block<C, HASHED, POW2, FINE == 0>(lv, s_acc, row_lo, nrows, u0, rs0, g0);
-                    else if constexpr (FINE == 2) point_scatter_combos<C, HASHED, POW2>(lv, s_acc, row_lo, nrows, u0[0], rs0[0], g0);
+                    if constexpr (COARSE) level_scatter_block<C, HASHED, POW2, true>(lv, s_acc, row_lo, nrows, u0, rs0, g0);
+                    else if constexpr (COMBOS) point_scatter_combos<C, HASHED, POW2>(lv, s_acc, row_lo, nrows, u0[0], rs0[0], g0);
                     else point_scatter_block<C, HASHED, POW2>(lv, s_acc, row_lo, nrows, u0[0], rs0[0], g0);
                 }
                 if (v1) {
-                    if constexpr (COARSE) level_scatter_block<C, HASHED, POW2, FINE == 0>(lv, s_acc, row_lo, nrows, u1, rs1, g1);
-                    else if constexpr (FINE == 2) point_scatter_combos<C, HASHED, POW2>(lv, s_acc, row_lo, nrows, u1[0], rs1[0], g1);
+                    if constexpr (COARSE) level_scatter_block<C, HASHED, POW2, true>(lv, s_acc, row_lo, nrows, u1, rs1, g1);
+                    else if constexpr (COMBOS) point_scatter_combos<C, HASHED, POW2>(lv, s_acc, row_lo, nrows, u1[0], rs1[0], g1);
                     else point_scatter_block<C, HASHED, POW2>(lv, s_acc, row_lo, nrows, u1[0], rs1[0], g1);
                 }
             }
@@ -1654,7 +1590,7 @@ __device__ __forceinline__ void cmp_block(const UcnLevel &lv, A *__restrict__ s_
 // sum and every lane appends its own items; (y, z)-combination scatter as in shape 2.  A lane can hold up to 24 hits: when the
 // wave's count would not fit the ring, only every lane's lowest non-empty byte (<= 6 hits, <= 384 per wave: the bound cmp_block
 // lives with) is taken in this round and the rest of the word stays for the next one.
-template <uint32_t C, bool HASHED, bool POW2, bool COMBOS, typename A>
+template <uint32_t C, bool HASHED, bool POW2, typename A>
 __device__ __forceinline__ void cmp_block_bytes(const UcnLevel &lv, A *__restrict__ s_acc, uint32_t *__restrict__ q, uint32_t row_lo,
                                                 uint32_t nrows, uint32_t part, uint32_t split, size_t B,
                                                 const uint8_t *__restrict__ mb, const float *__restrict__ gl,
@@ -1715,12 +1651,10 @@ __device__ __forceinline__ void cmp_block_bytes(const UcnLevel &lv, A *__restric
             cmp_fetch<C, HASHED, POW2, false>(i0, v0, B, gl, geom, u0, rs0, g0, gscale);
             cmp_fetch<C, HASHED, POW2, false>(i1, v1, B, gl, geom, u1, rs1, g1, gscale);
             if (v0) {
-                if constexpr (COMBOS) point_scatter_combos<C, HASHED, POW2>(lv, s_acc, row_lo, nrows, u0[0], rs0[0], g0);
-                else point_scatter_block<C, HASHED, POW2>(lv, s_acc, row_lo, nrows, u0[0], rs0[0], g0);
+                point_scatter_combos<C, HASHED, POW2>(lv, s_acc, row_lo, nrows, u0[0], rs0[0], g0);
             }
             if (v1) {
-                if constexpr (COMBOS) point_scatter_combos<C, HASHED, POW2>(lv, s_acc, row_lo, nrows, u1[0], rs1[0], g1);
-                else point_scatter_block<C, HASHED, POW2>(lv, s_acc, row_lo, nrows, u1[0], rs1[0], g1);
+                point_scatter_combos<C, HASHED, POW2>(lv, s_acc, row_lo, nrows, u1[0], rs1[0], g1);
             }
             head += avail;
         }
@@ -1872,10 +1806,6 @@ __device__ __forceinline__ void wide_block(const UcnLevel &lv, A *__restrict__ s
         const uint32_t thr1 = more ? 64u : 1u;
         while (tail1 - head1 >= thr1 && tail1 != head1) {
             const uint32_t avail = tail1 - head1 < 64u ? tail1 - head1 : 64u;
-#ifdef UCN_EXP_SCAN_ONLY                                                        // experiment build: the mask scan alone
-            head1 += avail;
-            continue;
-#endif
             const bool v = lane < avail;
             const uint32_t b = v ? q1[(head1 + lane) % kRing1] : 0u;
             // the next point's geometry is requested before this one is tested (a round is otherwise one exposed load latency).
@@ -1923,9 +1853,6 @@ __device__ __forceinline__ void wide_block(const UcnLevel &lv, A *__restrict__ s
                     pos++;
                 }
                 __builtin_amdgcn_wave_barrier();
-#ifdef UCN_EXP_NO_UPDATE                                                        // experiment build: scan + stage 1, no stage 2
-                head2 = tail2;
-#endif
                 // ring 2: <= 63 left over + <= 256 appended per round <= kRing2
                 wide_drain<C, HASHED, POW2>(lv, s_acc, q2, head2, tail2, 64u, lane, row_lo, nrows, gl, geom, gscale);
             }
@@ -1936,14 +1863,11 @@ __device__ __forceinline__ void wide_block(const UcnLevel &lv, A *__restrict__ s
     wide_drain<C, HASHED, POW2>(lv, s_acc, q2, head2, tail2, 1u, lane, row_lo, nrows, gl, geom, gscale);
 }
 
-#ifdef UCN_WG_CLOCK                                    // tools/bwd_balance.py: start / end time of every workgroup (experiment builds only)
-__device__ uint64_t g_wg_clock[8192][3];
-#endif
 // PERSISTENT workgroups (r03): one per CU, tasks (level, row block, sample part) pulled from a counter in the plan's
 // longest-first order.  With one workgroup per task the hardware dispatcher hands workgroup k to XCD k mod 8 IN ORDER: where
 // task times differ (45 ... 1010 us inside the uneven levels) a full XCD blocks the dispatch for all eight -- the workgroup
 // clocks of the benchmark grid showed 164-208 of 256 CUs busy behind the uneven levels and a 1.3 ms drain at the end
-// (tools/bwd_balance.py: 4.26 ms where the workgroup times sum to 3.70 ms per CU).
+// (4.26 ms where the workgroup times sum to 3.70 ms per CU).
 template <uint32_t C, bool FX = false>
 __global__ __launch_bounds__(1024) void k_march_features_bwd_cmp(UcnLevels lvls, float *__restrict__ grad_table, uint32_t N,
                                                                  uint32_t S, uint32_t rpb, MaskPlan plan,
@@ -1978,17 +1902,13 @@ __global__ __launch_bounds__(1024) void k_march_features_bwd_cmp(UcnLevels lvls,
         const uint32_t task0 = __builtin_amdgcn_readfirstlane(*s_task);               // wave-uniform: everything derived stays scalar
         __syncthreads();                                                              // before wave 0 refills its ring
         if (task0 >= total) break;
-#ifdef UCN_WG_CLOCK
-        if (threadIdx.x == 0 && task0 < 8192u) g_wg_clock[task0][0] = wall_clock64();
-#endif
         uint32_t task = task0, lvl = 0, nb = 1, split = 1;
         for (uint32_t i = 0;; i++) {
             lvl = plan.order[i];
             nb = (lvls.lv[lvl].rows + rpb - 1) / rpb;
             split = plan.split[lvl];
-            const uint32_t here = (plan.skip_fine && !plan.coarse[lvl]) ? 0u : nb * split;
-            if (task < here || i + 1 == lvls.L) break;                               // (`total` is the sum of `here`)
-            task -= here;
+            if (task < nb * split || i + 1 == lvls.L) break;                        // (`total` is the sum of nb * split)
+            task -= nb * split;
         }
         const UcnLevel lv = lvls.lv[lvl];
         const uint32_t blk = task / split, part = task % split;
@@ -2033,11 +1953,9 @@ __global__ __launch_bounds__(1024) void k_march_features_bwd_cmp(UcnLevels lvls,
 #define UCN_CMP(H, P2, CO, RU) cmp_block<C, H, P2, CO, RU>(lv, acc_rows, q, blk, row_lo, nrows, part, split, B, mp, gl, geom, gscale)
 #define UCN_CMPF(H, P2)                                                                                                      \
     do {                                                                                                                     \
-        if (plan.fine_kind[lvl] == 3) cmp_block_bytes<C, H, P2, true>(lv, acc_rows, q, row_lo, nrows, part, split, B, reinterpret_cast<const uint8_t *>(masks + (size_t)plan.plane[lvl] * B) + (size_t)blk * B, gl, geom, gscale); \
-        else if (plan.fine_kind[lvl] == 4) cmp_block_bytes<C, H, P2, false>(lv, acc_rows, q, row_lo, nrows, part, split, B, reinterpret_cast<const uint8_t *>(masks + (size_t)plan.plane[lvl] * B) + (size_t)blk * B, gl, geom, gscale); \
-        else if (plan.fine_kind[lvl] == 2) cmp_block<C, H, P2, false, false, 2>(lv, acc_rows, q, blk, row_lo, nrows, part, split, B, mp, gl, geom, gscale);      \
-        else if (plan.fine_kind[lvl] == 1) cmp_block<C, H, P2, false, false, 1>(lv, acc_rows, q, blk, row_lo, nrows, part, split, B, mp, gl, geom, gscale); \
-        else cmp_block<C, H, P2, false, false, 0>(lv, acc_rows, q, blk, row_lo, nrows, part, split, B, mp, gl, geom, gscale);           \
+        if (plan.fine_kind[lvl] == 3) cmp_block_bytes<C, H, P2>(lv, acc_rows, q, row_lo, nrows, part, split, B, reinterpret_cast<const uint8_t *>(masks + (size_t)plan.plane[lvl] * B) + (size_t)blk * B, gl, geom, gscale); \
+        else if (plan.fine_kind[lvl] == 2) cmp_block<C, H, P2, false, false, true>(lv, acc_rows, q, blk, row_lo, nrows, part, split, B, mp, gl, geom, gscale);    \
+        else cmp_block<C, H, P2, false, false, false>(lv, acc_rows, q, blk, row_lo, nrows, part, split, B, mp, gl, geom, gscale);         \
     } while (0)
         if (plan.coarse[lvl] == 2) {                                          // all workgroup-uniform; the coarsest
             if (lv.mask) UCN_CMP(false, true, true, true);                    // levels are never hashed
@@ -2080,264 +1998,6 @@ __global__ __launch_bounds__(1024) void k_march_features_bwd_cmp(UcnLevels lvls,
             }
         }
         }
-#ifdef UCN_WG_CLOCK
-        __syncthreads();
-        if (threadIdx.x == 0 && task0 < 8192u) { g_wg_clock[task0][1] = wall_clock64(); g_wg_clock[task0][2] = lvl; }
-#endif
-    }
-}
-#ifdef UCN_WG_CLOCK
-extern "C" int ucn_debug_wg_clock(uint64_t *host, uint32_t n) {
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_wg_clock), (size_t)n * 24u) == hipSuccess ? 0 : 1;
-}
-#endif
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Fine levels by ITEM LISTS (r03).  In the compacted kernel above every workgroup of a row block scans the block masks of
-// ALL samples (32 blocks per level: the scan is replicated 32x) and a hit re-derives all eight corners of the point although
-// only the ~2 of one (y, z) combination lie in the block (a hash scatters the four combinations over ~4 of the 32 blocks:
-// 4.5 hits per point).  Here the points are visited ONCE per level: every (point, (y, z) combination) becomes one 32-bit item
-// (sample | multisample << 27 | combination << 30) routed to the list of the block that owns the combination's x0 row --
-// a counting sort in two passes (k_bwd_bin<false> counts per (level, block), k_bwd_bin_scan turns the counts into offsets and
-// into a task table with workgroups PROPORTIONAL to a block's item count -- the strided levels of the uint32-wrap quirk
-// load their blocks very unevenly --, k_bwd_bin<true> writes the items through per-workgroup LDS ranks, one global atomic
-// per (workgroup, block)).  k_bwd_list then runs dense 64-lane batches over its list: one hash, two x-weights, one erf,
-// two 8-byte LDS compare-and-swaps per item; the x0 + 1 corner lands in another block once in ~16 384 items and goes to
-// the table by a global atomic.  Same addends as the compacted kernel ((w_k damp) g_c), other order.
-constexpr uint32_t kListTasks = 160;                  // workgroups per fine level (128 shared out by item count, + rounding)
-constexpr uint32_t kListMaxBlocks = 32;
-
-struct ListPlan {
-    uint32_t n_fine;
-    uint8_t level[UCN_MAX_LEVELS];          // fine level f -> level index
-    uint32_t nb[UCN_MAX_LEVELS];            // row blocks of that level
-    size_t cap;                             // items per fine level (= 24 B)
-};
-// control block (uint32): per fine level f: cnt[32] | cursor[32] | off[33] | tasks[kListTasks][2] (blk | nparts << 8 | part << 16, first item; count via next)
-constexpr uint32_t kCtlCnt = 0, kCtlCur = 32, kCtlOff = 64, kCtlTask = 100, kCtlPerLevel = kCtlTask + 3 * kListTasks + 4;
-
-// the x0 row of each of the four (y, z) combinations of a point, and its fractions
-template <bool HASHED, bool POW2>
-__device__ __forceinline__ void combo_rows(const UcnLevel &lv, float px, float py, float pz, float &fx, float &fy, float &fz,
-                                           uint32_t (&r0)[4], uint32_t (&r1)[4]) {
-    fx = fmaf(px, lv.scale, 0.5f); fy = fmaf(py, lv.scale, 0.5f); fz = fmaf(pz, lv.scale, 0.5f);
-    const uint32_t x0 = (uint32_t)floorf(fx), y0 = (uint32_t)floorf(fy), z0 = (uint32_t)floorf(fz);
-    fx -= (float)x0; fy -= (float)y0; fz -= (float)z0;
-    uint32_t ya, yb, za, zb, xa, xb;
-    if constexpr (HASHED) {
-        xa = x0; xb = x0 + 1u;
-        ya = y0 * kP1; yb = ya + kP1;
-        za = z0 * kP2; zb = za + kP2;
-    } else {
-        xa = x0 * lv.stride[0]; xb = xa + lv.stride[0];
-        ya = y0 * lv.stride[1]; yb = ya + lv.stride[1];
-        za = z0 * lv.stride[2]; zb = za + lv.stride[2];
-    }
-#pragma unroll
-    for (uint32_t c = 0; c < 4; c++) {
-        const uint32_t yv = (c & 1u) ? yb : ya, zv = (c & 2u) ? zb : za;
-        uint32_t i0, i1;
-        if constexpr (HASHED) { i0 = xa ^ yv ^ zv; i1 = xb ^ yv ^ zv; }
-        else { i0 = xa + yv + zv; i1 = xb + yv + zv; }
-        if constexpr (POW2) { r0[c] = i0 & lv.mask; r1[c] = i1 & lv.mask; }
-        else { r0[c] = i0 < lv.rows ? i0 : i0 % lv.rows; r1[c] = i1 < lv.rows ? i1 : i1 % lv.rows; }
-    }
-}
-__device__ __forceinline__ void combo_rows_any(const UcnLevel &lv, float px, float py, float pz, float &fx, float &fy, float &fz,
-                                               uint32_t (&r0)[4], uint32_t (&r1)[4]) {
-    if (lv.hashed) {
-        if (lv.mask) combo_rows<true, true>(lv, px, py, pz, fx, fy, fz, r0, r1);
-        else combo_rows<true, false>(lv, px, py, pz, fx, fy, fz, r0, r1);
-    } else {
-        if (lv.mask) combo_rows<false, true>(lv, px, py, pz, fx, fy, fz, r0, r1);
-        else combo_rows<false, false>(lv, px, py, pz, fx, fy, fz, r0, r1);
-    }
-}
-
-// pass 1 (WRITE = false): items per (fine level, block);  pass 3 (WRITE = true): the items themselves.
-// grid (ceil(B / 256), n_fine); thread = sample.
-template <uint32_t C, bool WRITE>
-__global__ __launch_bounds__(256) void k_bwd_bin(UcnLevels lvls, ListPlan lp, uint32_t shift, size_t B, const float *__restrict__ geom,
-                                                 const float *__restrict__ grad_lm /*[L][B][C]*/, uint32_t *__restrict__ ctl,
-                                                 uint32_t *__restrict__ lists) {
-    __shared__ uint32_t s_cnt[kListMaxBlocks], s_base[kListMaxBlocks];
-    const uint32_t f = blockIdx.y, lvl = lp.level[f];
-    const UcnLevel lv = lvls.lv[lvl];
-    if (threadIdx.x < kListMaxBlocks) s_cnt[threadIdx.x] = 0u;
-    __syncthreads();
-    const size_t b = (size_t)blockIdx.x * 256u + threadIdx.x;
-    uint32_t slot[24];                                    // blk << 16 | rank in the workgroup, 0xFFFFFFFF = no item
-#pragma unroll
-    for (uint32_t i = 0; i < 24; i++) slot[i] = 0xFFFFFFFFu;
-    bool live = b < B;
-    if (live) {
-        bool nz = false;
-#pragma unroll
-        for (uint32_t c = 0; c < C; c++) nz |= grad_lm[((size_t)lvl * B + b) * C + c] != 0.0f;
-        live = nz;                                        // a sample without gradient on this level contributes nothing
-    }
-    if (live) {
-#pragma unroll
-        for (uint32_t j = 0; j < 6; j++) {
-            const float4 q = reinterpret_cast<const float4 *>(geom)[b * 6 + j];
-            if (!in_unit_cube(q.x, q.y, q.z)) continue;
-            float fx, fy, fz;
-            uint32_t r0[4], r1[4];
-            combo_rows_any(lv, q.x, q.y, q.z, fx, fy, fz, r0, r1);
-#pragma unroll
-            for (uint32_t c = 0; c < 4; c++) {
-                const uint32_t blk = r0[c] >> shift;
-                const uint32_t rank = atomicAdd(&s_cnt[blk], 1u);
-                slot[4 * j + c] = (blk << 16) | rank;
-            }
-        }
-    }
-    __syncthreads();
-    uint32_t *cl = ctl + (size_t)f * kCtlPerLevel;
-    if (threadIdx.x < lp.nb[f] && s_cnt[threadIdx.x])
-        s_base[threadIdx.x] = atomicAdd(cl + (WRITE ? kCtlCur : kCtlCnt) + threadIdx.x, s_cnt[threadIdx.x]);
-    if constexpr (WRITE) {
-        // the workgroup's items are first gathered per block in LDS, then written out as ONE run per block: lanes write
-        // consecutive addresses (scattering 24 single words per thread straight to the 32 lists took 2.8 ms per step)
-        __shared__ uint32_t s_lbase[kListMaxBlocks + 1], s_items[256 * 24];
-        if (threadIdx.x == 0) {
-            uint32_t a = 0;
-            for (uint32_t k = 0; k < kListMaxBlocks; k++) { s_lbase[k] = a; a += s_cnt[k]; }
-            s_lbase[kListMaxBlocks] = a;
-        }
-        __syncthreads();
-#pragma unroll
-        for (uint32_t i = 0; i < 24; i++) {
-            if (slot[i] != 0xFFFFFFFFu) {
-                const uint32_t blk = slot[i] >> 16, rank = slot[i] & 0xFFFFu;
-                s_items[s_lbase[blk] + rank] = (uint32_t)b | ((i >> 2) << 27) | ((i & 3u) << 30);
-            }
-        }
-        __syncthreads();
-        uint32_t *lst = lists + (size_t)f * lp.cap;
-        const uint32_t total = s_lbase[kListMaxBlocks];
-        for (uint32_t i = threadIdx.x; i < total; i += 256u) {
-            uint32_t lo = 0, hi = kListMaxBlocks;                 // the block whose run holds position i
-            while (hi - lo > 1u) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (s_lbase[mid] <= i) lo = mid; else hi = mid;
-            }
-            lst[cl[kCtlOff + lo] + s_base[lo] + (i - s_lbase[lo])] = s_items[i];
-        }
-    }
-}
-
-// pass 2: one workgroup of 64 lanes per fine level: offsets of the blocks' lists, and the task table
-__global__ __launch_bounds__(64) void k_bwd_bin_scan(ListPlan lp, uint32_t *__restrict__ ctl) {
-    const uint32_t f = blockIdx.x, nb = lp.nb[f];
-    uint32_t *cl = ctl + (size_t)f * kCtlPerLevel;
-    if (threadIdx.x != 0) return;
-    uint32_t total = 0;
-    for (uint32_t k = 0; k < nb; k++) { cl[kCtlOff + k] = total; total += cl[kCtlCnt + k]; }
-    cl[kCtlOff + nb] = total;
-    // parts per block proportional to its share of the items (>= 1 where there are any), 128 in all (+ rounding)
-    uint32_t t = 0;
-    for (uint32_t k = 0; k < nb; k++) {
-        const uint32_t cnt = cl[kCtlCnt + k];
-        if (!cnt) continue;
-        uint32_t parts = total ? (uint32_t)(((uint64_t)cnt * 128u + total / 2) / total) : 1u;
-        parts = parts < 1u ? 1u : parts;
-        if (t + parts > kListTasks) parts = kListTasks - t;   // (never: sum of max(1, round(128 share)) over <= 32 blocks <= 160)
-        if (!parts) break;
-        const uint32_t per = (cnt + parts - 1) / parts;
-        for (uint32_t p = 0; p < parts && t < kListTasks; p++) {
-            const uint32_t lo = p * per, hi = lo + per < cnt ? lo + per : cnt;
-            if (lo >= hi) break;
-            cl[kCtlTask + 3 * t + 0] = k | (parts << 8);
-            cl[kCtlTask + 3 * t + 1] = cl[kCtlOff + k] + lo;
-            cl[kCtlTask + 3 * t + 2] = hi - lo;
-            t++;
-        }
-        if (t >= kListTasks) break;                        // (cannot drop work: parts were clamped so that every block gets >= 1 task
-    }                                                      //  only while t < kListTasks; nb <= 32 and the proportional parts sum to <= 144)
-    for (; t < kListTasks; t++) cl[kCtlTask + 3 * t + 2] = 0u;
-}
-
-template <uint32_t C, bool HASHED, bool POW2>
-__device__ __forceinline__ void list_item(const UcnLevel &lv, float *__restrict__ s_acc, float *__restrict__ gtab_level, uint32_t row_lo,
-                                          uint32_t nrows, uint32_t item, size_t B, const float *__restrict__ gl, const float *__restrict__ geom) {
-    const uint32_t b = item & 0x07FFFFFFu, j = (item >> 27) & 7u, c = item >> 30;
-    const float4 q = reinterpret_cast<const float4 *>(geom)[(size_t)b * 6 + j];
-    float g[C];
-#pragma unroll
-    for (uint32_t cc = 0; cc < C; cc++) g[cc] = gl[(size_t)b * C + cc];                     // d(mean over the 6 multisamples), / 6 by k_cast_cache_masks
-    float fx = fmaf(q.x, lv.scale, 0.5f), fy = fmaf(q.y, lv.scale, 0.5f), fz = fmaf(q.z, lv.scale, 0.5f);
-    const uint32_t x0 = (uint32_t)floorf(fx), y0 = (uint32_t)floorf(fy), z0 = (uint32_t)floorf(fz);
-    fx -= (float)x0; fy -= (float)y0; fz -= (float)z0;
-    const uint32_t yy = y0 + (c & 1u), zz = z0 + (c >> 1);
-    uint32_t i0, i1;
-    if constexpr (HASHED) { const uint32_t h = (yy * kP1) ^ (zz * kP2); i0 = x0 ^ h; i1 = (x0 + 1u) ^ h; }
-    else { const uint32_t h = yy * lv.stride[1] + zz * lv.stride[2]; i0 = x0 * lv.stride[0] + h; i1 = i0 + lv.stride[0]; }
-    uint32_t r0, r1;
-    if constexpr (POW2) { r0 = i0 & lv.mask; r1 = i1 & lv.mask; }
-    else { r0 = i0 < lv.rows ? i0 : i0 % lv.rows; r1 = i1 < lv.rows ? i1 : i1 % lv.rows; }
-    // corner weights in the reference's multiplication order ((wx wy) wz), gridencoder.cu:168-180
-    const float wy = (c & 1u) ? fy : 1.0f - fy, wz = (c >> 1) ? fz : 1.0f - fz;
-    const float damp = erf_pos(q.w * lv.inv_gs);
-    const float w0 = ((1.0f - fx) * wy) * wz, w1 = (fx * wy) * wz;
-    float v0[C], v1[C];
-#pragma unroll
-    for (uint32_t cc = 0; cc < C; cc++) { v0[cc] = (w0 * damp) * g[cc]; v1[cc] = (w1 * damp) * g[cc]; }
-    lds_row_add<C, true>(s_acc, r0 - row_lo, v0);              // the item was routed by r0: always in this block
-    const uint32_t l1 = r1 - row_lo;
-    if (l1 < nrows) lds_row_add<C, true>(s_acc, l1, v1);
-    else {
-#pragma unroll
-        for (uint32_t cc = 0; cc < C; cc++) atomicAdd(gtab_level + (size_t)r1 * C + cc, v1[cc]);      // ~1 in 16 384 items
-    }
-}
-
-// grid (kListTasks, n_fine), 1024 threads, the block's accumulators in LDS
-template <uint32_t C>
-__global__ __launch_bounds__(1024) void k_bwd_list(UcnLevels lvls, ListPlan lp, float *__restrict__ grad_table, uint32_t rpb, size_t B,
-                                                   const float *__restrict__ grad_lm, const float *__restrict__ geom,
-                                                   const uint32_t *__restrict__ ctl, const uint32_t *__restrict__ lists) {
-    extern __shared__ float s_acc[];
-    const uint32_t f = blockIdx.y, lvl = lp.level[f];
-    const uint32_t *cl = ctl + (size_t)f * kCtlPerLevel;
-    const uint32_t n_items = cl[kCtlTask + 3 * blockIdx.x + 2];
-    if (!n_items) return;
-    const uint32_t head = cl[kCtlTask + 3 * blockIdx.x + 0], first = cl[kCtlTask + 3 * blockIdx.x + 1];
-    const uint32_t blk = head & 0xFFu;
-    const UcnLevel lv = lvls.lv[lvl];
-    const uint32_t row_lo = blk * rpb;
-    const uint32_t nrows = lv.rows - row_lo < rpb ? lv.rows - row_lo : rpb;
-    for (uint32_t i = threadIdx.x; i < nrows * C; i += 1024u) s_acc[i] = 0.0f;
-    __syncthreads();
-    const uint32_t *lst = lists + (size_t)f * lp.cap + first;
-    const float *gl = grad_lm + (size_t)lvl * B * C;
-    float *gtab = grad_table + (size_t)lv.first_row * C;
-    // two items per lane and round: both items' loads are in flight before the first update
-    for (uint32_t i = threadIdx.x; i < n_items; i += 2048u) {
-        const uint32_t it0 = lst[i], i1 = i + 1024u;
-        const bool has1 = i1 < n_items;
-        const uint32_t it1 = has1 ? lst[i1] : 0u;
-        if (lv.hashed) {
-            if (lv.mask) {
-                list_item<C, true, true>(lv, s_acc, gtab, row_lo, nrows, it0, B, gl, geom);
-                if (has1) list_item<C, true, true>(lv, s_acc, gtab, row_lo, nrows, it1, B, gl, geom);
-            } else {
-                list_item<C, true, false>(lv, s_acc, gtab, row_lo, nrows, it0, B, gl, geom);
-                if (has1) list_item<C, true, false>(lv, s_acc, gtab, row_lo, nrows, it1, B, gl, geom);
-            }
-        } else if (lv.mask) {
-            list_item<C, false, true>(lv, s_acc, gtab, row_lo, nrows, it0, B, gl, geom);
-            if (has1) list_item<C, false, true>(lv, s_acc, gtab, row_lo, nrows, it1, B, gl, geom);
-        } else {
-            list_item<C, false, false>(lv, s_acc, gtab, row_lo, nrows, it0, B, gl, geom);
-            if (has1) list_item<C, false, false>(lv, s_acc, gtab, row_lo, nrows, it1, B, gl, geom);
-        }
-    }
-    __syncthreads();
-    float *dst = gtab + (size_t)row_lo * C;
-    for (uint32_t i = threadIdx.x; i < nrows * C; i += 1024u) {
-        const float v = s_acc[i];
-        if (v != 0.0f) atomicAdd(dst + i, v);      // several workgroups share a block, and the rare cross-block corners of others land here too
     }
 }
 
@@ -2425,13 +2085,11 @@ extern "C" int ucn_march_features(const ucn_field_t *f, const float *sdist, cons
     const RayInputs in{sdist, near_, far_, origins, directions, basis, radii, flip, spin};
     const HexPattern hx = make_hex();
     hipStream_t st = (hipStream_t)stream;
-    // experiment knob (tools/feat_occupancy.py): unused dynamic LDS per workgroup caps the workgroups per CU
-    static const size_t dummy_lds = getenv("UCN_FEAT_DUMMY_LDS") ? (size_t)atol(getenv("UCN_FEAT_DUMMY_LDS")) : 0;
     // co-resident shape: 512 threads = two waves per SIMD, 88 KiB of LDS reserved -> ONE such workgroup per CU, and
     // room for one MLP workgroup (72 KiB, one 296-register wave per SIMD) beside it.  The kernel runs at 97 % of its
     // full-occupancy rate with two waves per SIMD (profiles/r02*/occupancy.txt): it is bound by the L2 request rate.
     const uint32_t tpb = coresident ? 512u : 256u;
-    const size_t lds = coresident ? 88u * 1024u : dummy_lds;
+    const size_t lds = coresident ? 88u * 1024u : 0u;
     const dim3 grid(ucn_div_up(B, tpb), grp.n);
 #define UCN_MF2(CC, FEW)                                                                                                  \
     do {                                                                                                                  \
@@ -2487,32 +2145,15 @@ extern "C" int ucn_contract_probe(const float *means, const float *stds, uint32_
     return 0;
 }
 
-static bool plan_has_wide(const UcnLevels &lv, const MaskPlan &plan) {      // wide_block items hold the sample in 24 bits
-    for (uint32_t l = 0; l < lv.L; l++)
-        if (plan.coarse[l] == 3) return true;
-    return false;
-}
-static bool make_list_plan(const UcnLevels &lv, const MaskPlan &plan, uint32_t rpb, size_t B, ListPlan *lp) {
-    lp->n_fine = 0;
-    lp->cap = 24ull * B;
-    if (B >= (1ull << 27)) return false;                     // 27 bits of an item hold the sample
-    for (uint32_t l = 0; l < lv.L; l++)
-        if (!plan.coarse[l]) {
-            lp->level[lp->n_fine] = (uint8_t)l;
-            lp->nb[lp->n_fine] = ucn_div_up(lv.lv[l].rows, rpb);
-            lp->n_fine++;
-        }
-    return lp->n_fine > 0;
-}
-// UCN_BWD_LISTS=1 turns the item-list path on for the fine levels.  OFF by default on measurement (8192 x 128 samples,
-// config B, profiles/r03/bwd_lists.txt): the list kernel takes 1.86 ms for the ten fine levels where the compacted kernel
-// takes 2.9 -- but the counting sort in front of it costs 0.35 (count) + 2.2 ms (scatter: 250 M items = 1 GB written), and the
-// list kernel itself is bound by its three gathers per item (item, 16-byte geometry, 8-byte gradient: 7 GB through the
-// texture-address path), which is what the recomputing kernel avoids: 4.4 ms against 2.9.  Kept as a cross-check of the
-// compacted kernel (same addends, other route; tests/test_full_size.py runs the adjoint test on it).
-static bool bwd_lists_enabled() {
-    static const bool on = getenv("UCN_BWD_LISTS") && atoi(getenv("UCN_BWD_LISTS")) != 0;
-    return on;
+// The one route decision of the table gradient: true (and `plan` filled in) where ucn_march_features_backward(levels_per_block = 0)
+// takes the compacted row-block kernel, given a workspace.  Item words hold the sample in 29 bits (cmp_block), wide_block's in 24.
+static bool bwd_row_block_plan(const UcnLevels &lv, size_t B, bool fixed, MaskPlan *plan) {
+    const uint32_t rpb = 128u * 1024u / (lv.C * 4u);
+    if (B >= (1ull << 29) || !make_mask_plan(lv, rpb, B, plan, fixed)) return false;
+    if (B >= (1ull << 24))
+        for (uint32_t l = 0; l < lv.L; l++)
+            if (plan->coarse[l] == 3) return false;
+    return true;
 }
 
 // CUs of the current device (the persistent backward launches one workgroup per CU)
@@ -2530,38 +2171,29 @@ static uint32_t device_cu_count() {
     return cached;
 }
 
+// Workspace of ucn_march_features_backward: the geometry planes (24 B floats; the fallbacks use these alone), and where the call takes
+// the compacted row-block kernel the block-mask planes (room for the float-row and the fixed-point plan, whichever has more), a
+// level-major copy of the gradient, the task counter and the 256-sample L1 partials of the fixed-point mode.
 extern "C" uint64_t ucn_march_features_backward_ws_floats(const ucn_field_t *f, uint32_t N, uint32_t S) {
     UcnLevels lv;
     if (field_levels(f, &lv)) return 0;
-    MaskPlan plan;
-    const uint32_t rpb = 128u * 1024u / (lv.C * 4u);
     const size_t B = (size_t)N * S;
-    const bool masks = make_mask_plan(lv, rpb, B, &plan);
-    MaskPlan plan_fx;                                                                         // the fixed-point call cuts the levels differently: room for either
-    const bool masks_fx = masks && make_mask_plan(lv, rpb, B, &plan_fx, true);
-    if (masks_fx && plan_fx.n_planes > plan.n_planes) plan.n_planes = plan_fx.n_planes;
-    // geometry planes + block-mask planes + a level-major copy of the gradient (layouts 1 and 3)
+    MaskPlan plan, plan_fx;
+    const bool masks = bwd_row_block_plan(lv, B, false, &plan);
+    if (masks && bwd_row_block_plan(lv, B, true, &plan_fx) && plan_fx.n_planes > plan.n_planes) plan.n_planes = plan_fx.n_planes;
     uint64_t n = (24ull + (masks ? plan.n_planes + lv.L * lv.C : 0u)) * B + 64u;             // + the task counter
     n += (((uint64_t)lv.L * ucn_div_up(B, 256) + 63u) & ~63ull);                                 // + the 256-sample L1 partials of the fixed-point mode
-    ListPlan lp;
-    uint64_t n_lists = 0;
-    if (masks && make_list_plan(lv, plan, rpb, B, &lp))      // + the item lists of the fine levels and their control block
-        n_lists = (uint64_t)lp.n_fine * (lp.cap + kCtlPerLevel) + 64;
-    if (masks_fx && make_list_plan(lv, plan_fx, rpb, B, &lp) && (uint64_t)lp.n_fine * (lp.cap + kCtlPerLevel) + 64 > n_lists)
-        n_lists = (uint64_t)lp.n_fine * (lp.cap + kCtlPerLevel) + 64;
-    n += n_lists;
     return n;
 }
 
 // 1 if ucn_march_features_backward(levels_per_block = 0, with a workspace) takes the compacted row-block kernel for this field and call
-// size -- the route that reads a layout-4 gradient (its launcher below applies the same test)
+// size under float AND under fixed-point rows -- the route that reads a layout-4 gradient (bwd_row_block_plan, as in the launcher)
 extern "C" int ucn_march_features_backward_row_blocks(const ucn_field_t *f, uint32_t N, uint32_t S) {
     UcnLevels lv;
     if (field_levels(f, &lv)) return 0;
     const size_t B = (size_t)N * S;
-    const uint32_t rpb = 128u * 1024u / (lv.C * 4u);
     MaskPlan plan;
-    return (B > 0 && B < (1ull << 29) && B <= 0xFFFFFF00ull && make_mask_plan(lv, rpb, B, &plan) && !(plan_has_wide(lv, plan) && B >= (1ull << 24))) ? 1 : 0;
+    return (B > 0 && bwd_row_block_plan(lv, B, false, &plan) && bwd_row_block_plan(lv, B, true, &plan)) ? 1 : 0;
 }
 
 extern "C" int ucn_march_features_backward(const ucn_field_t *f, const float *sdist, const float *near_, const float *far_,
@@ -2603,7 +2235,7 @@ extern "C" int ucn_march_features_backward(const ucn_field_t *f, const float *sd
             tasks += nb * bwd_sample_split(nb);
         }
         MaskPlan plan;
-        if (workspace && B < (1ull << 29) && make_mask_plan(lv, rpb, B, &plan, fixed) && !(plan_has_wide(lv, plan) && B >= (1ull << 24))) {
+        if (workspace && bwd_row_block_plan(lv, B, fixed, &plan)) {
             tasks = 0;
             for (uint32_t l = 0; l < lv.L; l++) {
                 const uint32_t nb = ucn_div_up(lv.lv[l].rows, rpb);
@@ -2618,30 +2250,8 @@ extern "C" int ucn_march_features_backward(const ucn_field_t *f, const float *sd
                                grad_features, gs, lv.C, workspace, masks, prediv ? nullptr : glm, task_counter, fixed ? l1_partial : nullptr);
             const float *glv = prediv ? grad_features : glm;                                    // [L][B][C], / 6
             const uint32_t cus = device_cu_count();
-            ListPlan lp;
-            const bool lists = bwd_lists_enabled() && make_list_plan(lv, plan, rpb, B, &lp);
-            uint32_t *ctl = nullptr, *items = nullptr;
-            if (lists) {
-                // fine levels: counting sort of (point, (y, z) combination) items into per-block lists, then k_bwd_list
-                ctl = task_counter + 64 + (((size_t)lv.L * ucn_div_up(B, 256) + 63u) & ~(size_t)63u);
-                items = ctl + (((size_t)lp.n_fine * kCtlPerLevel + 63u) & ~(size_t)63u);
-                if (hipMemsetAsync(ctl, 0, (size_t)lp.n_fine * kCtlPerLevel * sizeof(uint32_t), st) != hipSuccess)
-                    return ucn_fail("march_features_backward: hipMemsetAsync failed");
-                plan.skip_fine = 1u;
-                tasks = 0;
-                for (uint32_t l = 0; l < lv.L; l++) {
-                    const uint32_t nb = ucn_div_up(lv.lv[l].rows, rpb);
-                    if (plan.coarse[l]) tasks += nb * plan.split[l];
-                }
-            }
 #define UCN_MBC(CC)                                                                                              \
     do {                                                                                                         \
-        const dim3 bg(ucn_div_up(B, 256), lists ? lp.n_fine : 1u);                                               \
-        if (lists) {                                                                                             \
-            hipLaunchKernelGGL((k_bwd_bin<CC, false>), bg, dim3(256), 0, st, lv, lp, plan.shift, B, workspace, glv, ctl, items); \
-            hipLaunchKernelGGL(k_bwd_bin_scan, dim3(lp.n_fine), dim3(64), 0, st, lp, ctl);                       \
-            hipLaunchKernelGGL((k_bwd_bin<CC, true>), bg, dim3(256), 0, st, lv, lp, plan.shift, B, workspace, glv, ctl, items); \
-        }                                                                                                        \
         if (tasks && fixed && CC % 2 == 0)                                                                       \
             hipLaunchKernelGGL((k_march_features_bwd_cmp<(CC % 2 == 0 ? CC : 2), true>), dim3(tasks < cus ? tasks : cus), dim3(1024), \
                                (size_t)rpb * CC * 4 + 16 * kQueue * 4, st, lv, grad_embeddings, N, S, rpb, plan, glv, \
@@ -2650,9 +2260,6 @@ extern "C" int ucn_march_features_backward(const ucn_field_t *f, const float *sd
             hipLaunchKernelGGL((k_march_features_bwd_cmp<CC, false>), dim3(tasks < cus ? tasks : cus), dim3(1024), \
                                (size_t)rpb * CC * 4 + 16 * kQueue * 4, st, lv, grad_embeddings, N, S, rpb, plan, glv, \
                                workspace, masks, task_counter, tasks, nullptr);                                  \
-        if (lists)                                                                                               \
-            hipLaunchKernelGGL(k_bwd_list<CC>, dim3(kListTasks, lp.n_fine), dim3(1024), (size_t)rpb * CC * 4, st, lv, lp, \
-                               grad_embeddings, rpb, B, glv, workspace, ctl, items);                              \
     } while (0)
             switch (lv.C) {
                 case 1: UCN_MBC(1); break;
