@@ -321,6 +321,15 @@ int ucn_bias_relu(void *pre_inout, const void *per_ray, uint32_t N, uint32_t S, 
 int ucn_relu_backward_reduce(const void *gy, const void *h, void *d_pre, void *d_per_ray, uint32_t N, uint32_t S,
                              uint32_t W, int dtype, ucn_stream_t stream);
 
+/* GLO appearance modulation of the bottleneck (models.py:606-614) in the training graph: ucn_ray_film: out [N*S, W] =
+ * x * a[ray] + b[ray] with a = exp(scale), b = shift as float32 [N, W] (fp32 arithmetic, the result rounded to dtype);
+ * ucn_ray_film_backward: gx = gy * a (dtype), ga [N, W] = sum over the ray's S samples of gy * x and gb = sum of gy, both
+ * float32, summed in a fixed order.  dtype 0 = float32, 2 = bfloat16 (autocast); W % 8 == 0 (W <= 2048 backward). */
+int ucn_ray_film(const void *x, const float *a, const float *b, void *out, uint32_t N, uint32_t S, uint32_t W, int dtype,
+                 ucn_stream_t stream);
+int ucn_ray_film_backward(const void *gy, const void *x, const float *a, void *gx, float *ga, float *gb, uint32_t N, uint32_t S,
+                          uint32_t W, int dtype, ucn_stream_t stream);
+
 /* Training-time forward of the NeRF field's dense layers in one kernel (models.py:507-674 under
  * accelerator.autocast(): bf16 operands, fp32 accumulation), writing every activation the backward needs once:
  * h0 [M,64], x [M,256] (bottleneck), h1, h2 [M,256] as bf16, raw [M] = x[:,0], y [M,3] = pre-sigmoid colour, M = N*S,

@@ -325,6 +325,73 @@ __global__ __launch_bounds__(256) void k_relu_bwd_reduce(const T *__restrict__ g
     }
 }
 
+// GLO bottleneck modulation (models.py:606-614): out = x * a[ray] + b[ray], a = exp(scale), b = shift as fp32 [N, W]; the
+// product and the sum are rounded separately (two fp32 ops, like the reference's eager mul + add), the result to the GEMM operand type.
+template <typename T>
+__global__ __launch_bounds__(256) void k_ray_film(const T *__restrict__ x, const float *__restrict__ a, const float *__restrict__ b,
+                                                  T *__restrict__ out, uint64_t total, uint32_t W, uint32_t S) {
+    const uint64_t i0 = ((uint64_t)blockIdx.x * 256u + threadIdx.x) * 8u;          // 8 consecutive columns of one row
+    if (i0 >= total) return;
+    const uint64_t row = i0 / W;
+    const uint32_t col = (uint32_t)(i0 - row * W);
+    const uint64_t r0 = (row / S) * W + col;
+    float v[8], sa[8], sb[8];
+    load8(x + i0, v);
+    load8(a + r0, sa);
+    load8(b + r0, sb);
+#pragma unroll
+    for (int k = 0; k < 8; k++) v[k] = rounded(v[k] * sa[k] + sb[k], out);
+    store8(out + i0, v);
+}
+
+// Its backward, one workgroup per ray: thread = (column group of 8, one of SL sample lanes), samples visited in a fixed order,
+// partial column sums meeting in LDS as in k_relu_bwd_reduce.  gx = gy * a (rounded to T); ga = sum_s gy * x, gb = sum_s gy in fp32.
+template <typename T>
+__global__ __launch_bounds__(256) void k_ray_film_bwd(const T *__restrict__ gy, const T *__restrict__ x, const float *__restrict__ a,
+                                                      T *__restrict__ gx, float *__restrict__ ga, float *__restrict__ gb, uint32_t S,
+                                                      uint32_t W) {
+    __shared__ float s_a[256 * 8], s_b[256 * 8];
+    const uint32_t ray = blockIdx.x, groups = W / 8u, lanes = 256u / groups;
+    const uint32_t cg = threadIdx.x % groups, sl = threadIdx.x / groups;
+    float acc_a[8] = {0, 0, 0, 0, 0, 0, 0, 0}, acc_b[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (sl < lanes) {
+        float sa[8];
+        load8(a + (uint64_t)ray * W + cg * 8u, sa);
+        for (uint32_t s = sl; s < S; s += lanes) {
+            const uint64_t i0 = ((uint64_t)ray * S + s) * W + cg * 8u;
+            float g[8], v[8];
+            load8(gy + i0, g);
+            load8(x + i0, v);
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                acc_a[k] += g[k] * v[k];
+                acc_b[k] += g[k];
+                v[k] = rounded(g[k] * sa[k], gx);
+            }
+            store8(gx + i0, v);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        s_a[threadIdx.x * 8 + k] = acc_a[k];
+        s_b[threadIdx.x * 8 + k] = acc_b[k];
+    }
+    __syncthreads();
+    if (sl == 0) {
+        float ta[8], tb[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            ta[k] = tb[k] = 0.0f;
+            for (uint32_t q = 0; q < lanes; q++) {
+                ta[k] += s_a[(q * groups + cg) * 8 + k];
+                tb[k] += s_b[(q * groups + cg) * 8 + k];
+            }
+        }
+        store8(ga + (uint64_t)ray * W + cg * 8u, ta);
+        store8(gb + (uint64_t)ray * W + cg * 8u, tb);
+    }
+}
+
 // Hash decay (models.py:297-306): mean over levels and channels of the per-level mean of embeddings^2 = sum over rows of
 // w_level * sum_c e^2 with w_level = 1 / (rows_of_level * L * C).  One pass over the table forward (block partials, added
 // in a fixed order by k_decay_finish), one pass backward (grad = 2 g w_level e).  As torch ops: pow + per-row sum + dot
@@ -570,5 +637,37 @@ extern "C" int ucn_relu_backward_reduce(const void *gy, const void *h, void *d_p
         hipLaunchKernelGGL(k_relu_bwd_reduce<Bf16>, dim3(N), dim3(256), 0, (hipStream_t)stream, (const Bf16 *)gy, (const Bf16 *)h,
                            (Bf16 *)d_pre, (Bf16 *)d_per_ray, S, W);
     UCN_LAUNCH_CHECK("relu_backward_reduce");
+    return 0;
+}
+
+extern "C" int ucn_ray_film(const void *x, const float *a, const float *b, void *out, uint32_t N, uint32_t S, uint32_t W, int dtype,
+                            ucn_stream_t stream) {
+    if ((uint64_t)N * S * W == 0) return 0;
+    UCN_REQUIRE(x && a && b && out, "ray_film: null pointer argument");
+    UCN_REQUIRE(W % 8 == 0, "ray_film: width must be a multiple of 8, got %u", W);
+    UCN_REQUIRE(dtype == 0 || dtype == 2, "ray_film: dtype must be 0 (float32) or 2 (bfloat16)");
+    const uint64_t total = (uint64_t)N * S * W;
+    const dim3 grid((uint32_t)((total / 8 + 255) / 256));
+    if (dtype == 0)
+        hipLaunchKernelGGL(k_ray_film<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float *)x, a, b, (float *)out, total, W, S);
+    else
+        hipLaunchKernelGGL(k_ray_film<Bf16>, grid, dim3(256), 0, (hipStream_t)stream, (const Bf16 *)x, a, b, (Bf16 *)out, total, W, S);
+    UCN_LAUNCH_CHECK("ray_film");
+    return 0;
+}
+
+extern "C" int ucn_ray_film_backward(const void *gy, const void *x, const float *a, void *gx, float *ga, float *gb, uint32_t N, uint32_t S,
+                                     uint32_t W, int dtype, ucn_stream_t stream) {
+    if ((uint64_t)N * W == 0) return 0;
+    UCN_REQUIRE(gy && x && a && gx && ga && gb, "ray_film_backward: null pointer argument");
+    UCN_REQUIRE(W % 8 == 0 && W / 8 <= 256, "ray_film_backward: width must be a multiple of 8 up to 2048, got %u", W);
+    UCN_REQUIRE(dtype == 0 || dtype == 2, "ray_film_backward: dtype must be 0 (float32) or 2 (bfloat16)");
+    if (dtype == 0)
+        hipLaunchKernelGGL(k_ray_film_bwd<float>, dim3(N), dim3(256), 0, (hipStream_t)stream, (const float *)gy, (const float *)x, a,
+                           (float *)gx, ga, gb, S, W);
+    else
+        hipLaunchKernelGGL(k_ray_film_bwd<Bf16>, dim3(N), dim3(256), 0, (hipStream_t)stream, (const Bf16 *)gy, (const Bf16 *)x, a,
+                           (Bf16 *)gx, ga, gb, S, W);
+    UCN_LAUNCH_CHECK("ray_film_backward");
     return 0;
 }

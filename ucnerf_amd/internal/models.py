@@ -9,7 +9,8 @@ signature: a sampling level is five kernel launches on the caller's HIP stream
 composite) instead of ~300 eager ops, and nothing of size [N*S*6, .] is ever materialised.
 
 Supported configuration = the reference's shipped one (configs/waymo.gin): disable_density_normals,
-no GLO, no reflections / diffuse / IDE, raydist_fn=None.  Anything else raises at construction.
+no reflections / diffuse / IDE, raydist_fn=None, plus GLO appearance codes (num_glo_features > 0; DESIGN.md
+"GLO").  Anything else raises at construction.
 In eval mode or with gradients disabled forward is the fused inference march; a model in training mode
 with gradients enabled routes to internal/train_graph.py (same kernels for resampling and featurisation, HIP
 backward for the tables and the dense layers' dgrad, autograd glue; `Model.march_route`).  Without the HIP library or a GPU every entry point raises.
@@ -56,6 +57,20 @@ def _f32(t, n, c):
     if t.dtype != torch.float32:
         t = t.float()
     return t.contiguous()
+
+
+def glo_fold(W0, b0, W1, b1, a, b):
+    """The colour layers (lin_second_stage_0 over [bottleneck, dir_enc], lin_second_stage_1 over [h1, bottleneck, dir_enc])
+    with a modulation x' = x * a + b of the bottleneck that is the SAME for every ray (a, b [NB]) folded into their weights:
+        W0x <- W0x diag(a),  b0 <- b0 + W0x b;   W1x <- W1x diag(a),  b1 <- b1 + W1x b
+    Exact in real arithmetic; returns new (W0, b0, W1, b1) in the parameters' dtype."""
+    NB, NW = a.numel(), W0.shape[0]
+    a, b = a.to(W0.dtype).reshape(-1), b.to(W0.dtype).reshape(-1)
+    W0x, W1x = W0[:, :NB], W1[:, NW:NW + NB]
+    W0f, W1f = W0.clone(), W1.clone()
+    W0f[:, :NB] = W0x * a
+    W1f[:, NW:NW + NB] = W1x * a
+    return W0f, b0 + W0x @ b, W1f, b1 + W1x @ b
 
 
 _U_CACHE = {}
@@ -128,7 +143,7 @@ class MLP(nn.Module):
         unsupported = dict(use_reflections=False, use_directional_enc=False, enable_pred_roughness=False,
                            use_diffuse_color=False, use_specular_tint=False, use_n_dot_v=False,
                            enable_pred_normals=False, disable_density_normals=True, scale_featurization=False,
-                           num_glo_features=0, net_depth_viewdirs=2, skip_layer_dir=0, num_rgb_channels=3,
+                           net_depth_viewdirs=2, skip_layer_dir=0, num_rgb_channels=3,
                            warp_fn='contract', bottleneck_noise=0.0, density_noise=0.0)
         for k, want in unsupported.items():
             if getattr(self, k) != want:
@@ -147,6 +162,12 @@ class MLP(nn.Module):
         self.dim_dir_enc = 3 + 6 * self.deg_view
         if not self.disable_rgb:
             last_dim_rgb = self.bottleneck_width + self.dim_dir_enc
+            if self.num_glo_features > 0:            # ref models.py:467-473: registered before the colour layers
+                last_dim_glo = self.num_glo_features
+                for i in range(self.net_depth_glo - 1):
+                    self.register_module(f"lin_glo_{i}", nn.Linear(last_dim_glo, self.net_width_glo))
+                    last_dim_glo = self.net_width_glo
+                self.register_module(f"lin_glo_{self.net_depth_glo - 1}", nn.Linear(last_dim_glo, self.bottleneck_width * 2))
             input_dim_rgb = last_dim_rgb
             for i in range(self.net_depth_viewdirs):
                 lin = nn.Linear(last_dim_rgb, self.net_width_viewdirs)
@@ -156,9 +177,45 @@ class MLP(nn.Module):
                 if i == self.skip_layer_dir:
                     last_dim_rgb += input_dim_rgb
             self.rgb_layer = nn.Linear(last_dim_rgb, self.num_rgb_channels)
-        self._fields = {}          # mlp_mode -> (key, ucn_field_t, packed weight stream): one packed buffer per mode
+        self._fields = {}          # (mlp_mode, glo fold) -> (key, ucn_field_t, packed weight stream): one packed buffer each
 
-    _UNPICKLED = ('_fields', '_grid_desc', '_grid_desc_key')
+    _UNPICKLED = ('_fields', '_grid_desc', '_grid_desc_key', '_glo_fold')
+
+    # ---- GLO appearance codes (ref models.py:600-614) ---------------------------------------------
+    def uses_glo(self):
+        return self.num_glo_features > 0 and not self.disable_rgb
+
+    def _glo_layers(self):
+        return [self.get_submodule(f"lin_glo_{i}") for i in range(self.net_depth_glo)]
+
+    def glo_affine(self, glo_vec):
+        """glo_vec [N, num_glo_features] -> (a = exp(scale), b = shift), float32 [N, bottleneck_width]: the per-ray GLO MLP
+        (lin_glo_0 -> ReLU -> ... -> lin_glo_last, models.py:606-612) in torch, differentiable.  Per ray, not per sample
+        (0.1 GFLOP at 8192 rays): not on the hot path."""
+        g = glo_vec
+        layers = self._glo_layers()
+        for i, lin in enumerate(layers):
+            g = lin(g)
+            if i != len(layers) - 1:
+                g = torch.relu(g)
+        scale, shift = g.chunk(2, dim=-1)
+        return torch.exp(scale).float().contiguous(), shift.float().contiguous()
+
+    def _glo_folded(self):
+        """The colour layers with the zero-code modulation folded in (glo_fold), float32 (W0, b0, W1, b1): what the fused
+        inference kernels run when every ray's code is zero (zero_glo=True).  Recomputed only when a parameter changed."""
+        l0, l1 = self.lin_second_stage_0, self.lin_second_stage_1
+        ps = [l0.weight, l0.bias, l1.weight, l1.bias] + [p for lin in self._glo_layers() for p in (lin.weight, lin.bias)]
+        key = tuple((p.data_ptr(), p._version) for p in ps)
+        hit = getattr(self, '_glo_fold', None)
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        with torch.no_grad(), torch.autocast('cuda', enabled=False):
+            z = torch.zeros(1, self.num_glo_features, device=l0.weight.device)
+            a, b = self.glo_affine(z)
+            out = tuple(t.contiguous() for t in glo_fold(l0.weight, l0.bias, l1.weight, l1.bias, a[0], b[0]))
+        self._glo_fold = (key, out)
+        return out
 
     def __getstate__(self):
         """copy.deepcopy / torch.save(model): the cached C descriptors hold raw device pointers (ctypes objects with
@@ -170,26 +227,32 @@ class MLP(nn.Module):
         return state
 
     # ---- C-ABI descriptor -------------------------------------------------------------------
-    def _weights(self):
+    def _weights(self, glo_fold=False):
         ws = [self.encoder.embeddings, self.density_layer[0].weight, self.density_layer[0].bias,
               self.density_layer[2].weight, self.density_layer[2].bias]
         if not self.disable_rgb:
-            ws += [self.lin_second_stage_0.weight, self.lin_second_stage_0.bias, self.lin_second_stage_1.weight,
-                   self.lin_second_stage_1.bias, self.rgb_layer.weight, self.rgb_layer.bias]
+            colour = [self.lin_second_stage_0.weight, self.lin_second_stage_0.bias, self.lin_second_stage_1.weight,
+                      self.lin_second_stage_1.bias]
+            ws += (list(self._glo_folded()) if glo_fold else colour) + [self.rgb_layer.weight, self.rgb_layer.bias]
         return ws
 
-    def field(self, mode=None):
+    def field(self, mode=None, glo_fold=False):
         """ucn_field_t for the current parameters and the given arithmetic mode (default: self.mlp_mode); the
         MFMA-ordered weight copy of that mode is refreshed when any parameter was updated in place or moved
-        (render: once; train: once per optimiser step)."""
+        (render: once; train: once per optimiser step).  glo_fold: the colour layers with the zero GLO code's modulation
+        folded in (a GLO field marched with zero_glo=True; the key then also covers lin_glo_*)."""
         mode = int(self.mlp_mode if mode is None else mode)
-        ws = self._weights()
+        glo_fold = bool(glo_fold) and self.uses_glo()
+        ws = self._weights(glo_fold)
         for w in ws:
             _lib.require_device(w, f"{type(self).__name__} parameter")
             if w.dtype != torch.float32 or not w.is_contiguous():
                 raise RuntimeError("field parameters must be contiguous float32")
         key = tuple((w.data_ptr(), w._version) for w in ws)
-        hit = self._fields.get(mode)
+        if glo_fold:
+            key += self._glo_fold[0]             # the folded copies are new tensors: their source parameters decide
+        mode_key = (mode, glo_fold) if glo_fold else mode
+        hit = self._fields.get(mode_key)
         if hit is not None and hit[0] == key:
             return hit[1]
         lib = _lib.load()
@@ -217,7 +280,7 @@ class MLP(nn.Module):
             packed = torch.empty(n, dtype=torch.float32, device=ws[0].device)
         d.packed = packed.data_ptr()
         _lib.check(lib.ucn_field_pack(ctypes.byref(d), _lib.stream()))
-        self._fields[mode] = (key, d, packed)
+        self._fields[mode_key] = (key, d, packed)
         return d
 
     def grid_field(self):
@@ -248,12 +311,36 @@ class MLP(nn.Module):
     @torch.no_grad()
     def forward(self, rand, means, stds, viewdirs=None, imageplane=None, glo_vec=None, exposure=None,
                 no_warp=False):
-        """ref models.py:514-685 (keys of the returned dict identical)."""
+        """ref models.py:514-685 (keys of the returned dict identical).  With glo_vec [..., num_glo_features] (one code per
+        ray) on a GLO field, the colour layers read the modulated bottleneck (models.py:606-614): the training graph's colour
+        node (_ColourMLPGlo) on the fp32 kernel's bottleneck, without gradients."""
+        if glo_vec is not None and self.uses_glo() and viewdirs is not None:
+            return self._forward_glo(means, stds, viewdirs, glo_vec, no_warp)
         _, _, coord, density, rgb = self._evaluate(means, stds, viewdirs, no_warp, want_x=False)
         if self.disable_rgb or viewdirs is None:
             rgb = torch.zeros(density.shape + (3,), device=density.device)
         return dict(coord=coord, density=density, rgb=rgb, raw_grad_density=None, grad_pred=None, normals=None,
                     normals_pred=None, roughness=None)
+
+    def _forward_glo(self, means, stds, viewdirs, glo_vec, no_warp):
+        from . import train_graph as tg
+        raw, x, coord = self.predict_density(means, stds, no_warp=no_warp)
+        prefix = raw.shape
+        vd = _f32(viewdirs, -1, 3)
+        N = vd.shape[0]
+        B = raw.numel()
+        if B % N:
+            raise RuntimeError("viewdirs do not divide the sample count")
+        density = torch.nn.functional.softplus(raw + self.density_bias)
+        with torch.autocast('cuda', enabled=False):
+            a, b = self.glo_affine(glo_vec.reshape(N, -1).float())
+            l0, l1 = self.lin_second_stage_0, self.lin_second_stage_1
+            h, _ = tg._ColourMLPGlo.apply(x.reshape(B, -1), a, b, tg.view_encoding(vd, self.deg_view), l0.weight, l0.bias,
+                                          l1.weight, l1.bias, N, B // N)
+            logits = torch.nn.functional.linear(h, self.rgb_layer.weight, self.rgb_layer.bias)
+        rgb = torch.sigmoid(self.rgb_premultiplier * logits + self.rgb_bias) * (1 + 2 * self.rgb_padding) - self.rgb_padding
+        return dict(coord=coord, density=density, rgb=rgb.reshape(prefix + (3,)), raw_grad_density=None, grad_pred=None,
+                    normals=None, normals_pred=None, roughness=None)
 
     def _evaluate(self, means, stds, viewdirs, no_warp, want_x):
         # the split-f16 kernel composes the bottleneck away; the API that returns it uses the fp32 kernel's packed copy
@@ -387,7 +474,7 @@ class Model(nn.Module):
         super().__init__()
         set_kwargs(self, kwargs)
         self.config = config
-        for k, want in dict(raydist_fn=None, num_glo_features=0, learned_exposure_scaling=False,
+        for k, want in dict(raydist_fn=None, learned_exposure_scaling=False,
                             near_anneal_rate=None, single_mlp=False, distinct_prop=True, use_viewdirs=True).items():
             if getattr(self, k) != want:
                 raise NotImplementedError(f"Model.{k}={getattr(self, k)!r} is outside the shipped waymo.gin path")
@@ -396,6 +483,9 @@ class Model(nn.Module):
         self.nerf_mlp = NerfMLP(num_glo_features=self.num_glo_features, num_glo_embeddings=self.num_glo_embeddings)
         for i in range(self.num_levels - 1):
             self.register_module(f'prop_mlp_{i}', PropMLP(grid_disired_resolution=self.prop_desired_grid_size[i]))
+        if self.num_glo_features > 0 and not getattr(config, 'zero_glo', False):
+            # ref models.py:73-75: one appearance code per training image, looked up by batch['cam_idx']
+            self.glo_vecs = nn.Embedding(self.num_glo_embeddings, self.num_glo_features)
         if getattr(self.config, 'model_sky', False):
             self.skynerf = NeRF(D=8, d_in_view=3, W=256, multires_view=4, output_ch=4, skips=[4])
         if getattr(self.config, 'brightness_correction', False):
@@ -417,9 +507,16 @@ class Model(nn.Module):
         route = self.march_route
         if route not in ('auto', 'train', 'inference'):
             raise ValueError(f"Model.march_route={route!r}: expected 'auto', 'train' or 'inference'")
+        glo_vec = self._glo_vec(batch, zero_glo)
         if route == 'train' or (route == 'auto' and self.training and torch.is_grad_enabled()):
             from . import train_graph
-            return train_graph.march_train(self, rand, batch, train_frac, compute_extras, eval_camidx)
+            return train_graph.march_train(self, rand, batch, train_frac, compute_extras, eval_camidx, glo_vec)
+        if glo_vec is not None and not zero_glo:
+            # per-ray codes differ: no call-wide fold exists, so the inference route is the training graph's forward without
+            # gradients (correct, slower than the fused march: the fused field kernels cannot take a per-ray scale; DESIGN.md GLO)
+            from . import train_graph
+            with torch.no_grad():
+                return train_graph.march_train(self, rand, batch, train_frac, compute_extras, eval_camidx, glo_vec)
         if route == 'auto' and torch.is_grad_enabled() and not self.training and not Model._warned_eval_route:
             Model._warned_eval_route = True
             import warnings
@@ -427,6 +524,20 @@ class Model(nn.Module):
                           "call model.train() before a training step, or set Model.march_route = 'train'", stacklevel=2)
         with torch.no_grad():
             return self._march(rand, batch, train_frac, compute_extras, eval_camidx, want_history=True)
+
+    def _glo_vec(self, batch, zero_glo):
+        """ref models.py:118-127: the NeRF level's per-ray GLO codes [N, num_glo_features] (zeros with zero_glo), or None."""
+        if not self.num_glo_features > 0:
+            return None
+        origins = batch['origins']
+        N = origins.numel() // origins.shape[-1]
+        if zero_glo:
+            return torch.zeros(N, self.num_glo_features, device=origins.device)
+        if not hasattr(self, 'glo_vecs'):
+            raise RuntimeError("Model.forward(zero_glo=False) on a model built with config.zero_glo=True: it has no glo_vecs "
+                               "(per-image GLO codes); pass zero_glo=True or build the model with config.zero_glo=False")
+        cam_idx = batch['cam_idx'][..., 0]
+        return self.glo_vecs(cam_idx.long()).reshape(N, self.num_glo_features)
 
     def _mixed_level(self, mlp, is_prop, F_in):
         """Mixed-precision inference of one level (see `autocast_render`): None = the fp32-class path, else what the bf16
@@ -463,8 +574,10 @@ class Model(nn.Module):
                 out['prop'] = tuple(t.detach().float().contiguous() for t in (l0.weight, l0.bias, l1.weight, l1.bias))
             else:
                 d0, d1, c0, c1, lr = mlp.density_layer[0], mlp.density_layer[2], mlp.lin_second_stage_0, mlp.lin_second_stage_1, mlp.rgb_layer
-                packed, _, We, be, bias0, bias1, biasr = tg.prepare_heads(d0.weight, d0.bias, d1.weight, d1.bias, c0.weight, c0.bias,
-                                                                         c1.weight, c1.bias, lr.weight, lr.bias, dir_in_stream=True)
+                # a GLO field: the zero code's modulation folded into the colour layers (every inference march here is zero_glo)
+                W0, b0, W1, b1 = mlp._glo_folded() if mlp.uses_glo() else (c0.weight, c0.bias, c1.weight, c1.bias)
+                packed, _, We, be, bias0, bias1, biasr = tg.prepare_heads(d0.weight, d0.bias, d1.weight, d1.bias, W0, b0,
+                                                                         W1, b1, lr.weight, lr.bias, dir_in_stream=True)
                 out.update(packed=packed, We=We, be=be, bias0=bias0, bias1=bias1, biasr=biasr, NW=c0.weight.shape[0],
                            head=(ctypes.c_float * 4)(float(mlp.density_bias), float(mlp.rgb_premultiplier), float(mlp.rgb_bias),
                                                      float(mlp.rgb_padding)),
@@ -498,7 +611,8 @@ class Model(nn.Module):
             anneal = (self.anneal_slope * train_frac) / ((self.anneal_slope - 1) * train_frac + 1)
         else:
             anneal = 1.
-        nerf_desc = self.nerf_mlp.field()
+        self.last_march_route = 'fused'       # diagnostics / tests: the route of the last forward (train_graph: 'train_graph')
+        nerf_desc = self.nerf_mlp.field(glo_fold=True)          # a GLO field: zero codes folded into the colour layers
         dirb = torch.empty(lib.ucn_field_dir_floats(ctypes.byref(nerf_desc), N), device=dev)
         _lib.check(lib.ucn_field_dir_bias(ctypes.byref(nerf_desc), vd.data_ptr(), N, dirb.data_ptr(), st))
 
@@ -512,7 +626,7 @@ class Model(nn.Module):
             is_prop = i_level < self.num_levels - 1
             S = self.num_prop_samples if is_prop else self.num_nerf_samples
             mlp = self.get_submodule(f'prop_mlp_{i_level}') if is_prop else self.nerf_mlp
-            desc = mlp.field()
+            desc = mlp.field(glo_fold=not is_prop)
             L, C = mlp.encoder.num_levels, mlp.encoder.level_dim
             # max_chunk_rays is quoted for the NeRF level; a proposal level (fewer samples, narrower features) takes
             # proportionally more rays per pass -- the same workspace bytes, fewer and longer launches

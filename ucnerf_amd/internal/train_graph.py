@@ -251,80 +251,136 @@ class _ColourMLP(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, enc, W0, b0, W1, b1, N, S):
-        lib = _lib.load()
-        dt = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled() else torch.float32
-        code = {torch.float32: 0, torch.bfloat16: 2}[dt]
-        NB, NW = x.shape[1], W0.shape[0]
-        hip = code == 0 and x.is_cuda and not dense_f32.library_route()      # fp32: csrc/gemm_f32.hip instead of the library GEMMs
-        with torch.autocast("cuda", enabled=False):
-            xb, eb = x.to(dt).contiguous(), enc.to(dt)
-            W0x, W0e = W0[:, :NB].to(dt), W0[:, NB:].to(dt)
-            W1h, W1x, W1e = W1[:, :NW].to(dt), W1[:, NW:NW + NB].to(dt), W1[:, NW + NB:].to(dt)
-            if hip:
-                R, G = dense_f32._rows, dense_f32.gemm
-                xb, eb = R(xb), R(eb)
-                W0x, W1h, W1x = R(W0x), R(W1h), R(W1x)
-                pr0 = G(eb, R(W0e), b0.contiguous())                                     # [N, NW] per ray
-                h1 = G(xb, W0x)
-                _lib.check(lib.ucn_bias_relu(h1.data_ptr(), pr0.data_ptr(), N, S, NW, code, _lib.stream()))
-                dense_f32.forget(h1)                                                     # written through its raw pointer
-                pr1 = G(eb, R(W1e), b1.contiguous())
-                h2 = G(h1, W1h)
-                G(xb, W1x, flags=dense_f32.ACCUMULATE, out=h2)                           # accumulate in place: no copy
-                _lib.check(lib.ucn_bias_relu(h2.data_ptr(), pr1.data_ptr(), N, S, NW, code, _lib.stream()))
-                dense_f32.forget(h2)
-            else:
-                pr0 = torch.addmm(b0.to(dt), eb, W0e.t()).contiguous()                   # [N, NW] per ray
-                h1 = xb @ W0x.t()
-                _lib.check(lib.ucn_bias_relu(h1.data_ptr(), pr0.data_ptr(), N, S, NW, code, _lib.stream()))
-                pr1 = torch.addmm(b1.to(dt), eb, W1e.t()).contiguous()
-                h2 = (h1 @ W1h.t()).addmm_(xb, W1x.t())                                  # accumulate in place: no copy
-                _lib.check(lib.ucn_bias_relu(h2.data_ptr(), pr1.data_ptr(), N, S, NW, code, _lib.stream()))
-        ctx.save_for_backward(xb, eb, h1, h2, W0x, W1h, W1x)
-        ctx.meta = (N, S, NB, NW, code, x.dtype, W0.dtype, b0.dtype, hip, enc.shape[1])
+        h2, xb, saved, meta = _colour_mlp_forward(x, enc, W0, b0, W1, b1, N, S)
+        ctx.save_for_backward(*saved)
+        ctx.meta = meta
         return h2, xb[:, 0].clone()                       # raw density = column 0 of the bottleneck (models.py:508)
 
     @staticmethod
     def backward(ctx, g_h2, g_raw):
-        lib = _lib.load()
-        xb, eb, h1, h2, W0x, W1h, W1x = ctx.saved_tensors
-        N, S, NB, NW, code, x_dt, w_dt, b_dt, hip, E = ctx.meta
-        dt = xb.dtype
-        with torch.autocast("cuda", enabled=False):
-            g = g_h2.to(dt).contiguous()
-            d1 = torch.empty_like(g)
-            r1 = torch.empty(N, NW, device=g.device, dtype=dt)
-            _lib.check(lib.ucn_relu_backward_reduce(g.data_ptr(), h2.data_ptr(), d1.data_ptr(), r1.data_ptr(), N, S, NW, code,
-                                                    _lib.stream()))
-            if hip:
-                # the same node on the hand-written fp32 kernels: dgrad = the forward kernel on the transposed weight; every
-                # weight gradient one pass of ucn_wgrad_f32 (fixed-order partial sums); both paths into x accumulate in one output
-                R, G, WG = dense_f32._rows, dense_f32.gemm, dense_f32.wgrad
-                d0 = G(d1, R(W1h.t()))                                                    # d h1, masked in place below
-                r0 = torch.empty(N, NW, device=g.device, dtype=dt)
-                _lib.check(lib.ucn_relu_backward_reduce(d0.data_ptr(), h1.data_ptr(), d0.data_ptr(), r0.data_ptr(), N, S, NW, code,
-                                                        _lib.stream()))
-                dense_f32.forget(d0)                                                      # masked in place through its raw pointer
-                gW0 = torch.cat([WG(d0, xb)[0][:, :NB], WG(r0, eb)[0][:, :E]], dim=1)
-                gW1 = torch.cat([WG(d1, h1)[0], WG(d1, xb)[0][:, :NB], WG(r1, eb)[0][:, :E]], dim=1)
-                gb0, gb1 = r0.sum(0), r1.sum(0)
-                gx = G(d1, R(W1x[:, :NB].t()))
-                G(d0, R(W0x[:, :NB].t()), flags=dense_f32.ACCUMULATE, out=gx)
-                if g_raw is not None:
-                    gx[:, 0] += g_raw.reshape(-1)
-                return gx[:, :NB].to(x_dt), None, gW0.to(w_dt), gb0.to(b_dt), gW1.to(w_dt), gb1.to(b_dt), None, None
-            d_h1 = d1 @ W1h
-            d0 = d_h1                                                                     # masked in place
+        gx, gW0, gb0, gW1, gb1 = _colour_mlp_backward(ctx.saved_tensors, ctx.meta, g_h2, g_raw)
+        return gx, None, gW0, gb0, gW1, gb1, None, None
+
+
+def _colour_mlp_forward(x, enc, W0, b0, W1, b1, N, S, film=None):
+    """_ColourMLP's forward: (h2, the bottleneck operand as the GEMMs read it, tensors to save, meta).  film = (a, b), float32 [N, NB]:
+    the GEMMs read x * a[ray] + b[ray] (ucn_ray_film, the GLO modulation) instead of x."""
+    lib = _lib.load()
+    dt = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled() else torch.float32
+    code = {torch.float32: 0, torch.bfloat16: 2}[dt]
+    NB, NW = x.shape[1], W0.shape[0]
+    hip = code == 0 and x.is_cuda and not dense_f32.library_route()      # fp32: csrc/gemm_f32.hip instead of the library GEMMs
+    with torch.autocast("cuda", enabled=False):
+        xb, eb = x.to(dt).contiguous(), enc.to(dt)
+        if film is not None:
+            y = torch.empty_like(xb)
+            _lib.check(lib.ucn_ray_film(xb.data_ptr(), film[0].data_ptr(), film[1].data_ptr(), y.data_ptr(), N, S, NB, code,
+                                        _lib.stream()))
+            xb = y
+        W0x, W0e = W0[:, :NB].to(dt), W0[:, NB:].to(dt)
+        W1h, W1x, W1e = W1[:, :NW].to(dt), W1[:, NW:NW + NB].to(dt), W1[:, NW + NB:].to(dt)
+        if hip:
+            R, G = dense_f32._rows, dense_f32.gemm
+            xb, eb = R(xb), R(eb)
+            W0x, W1h, W1x = R(W0x), R(W1h), R(W1x)
+            pr0 = G(eb, R(W0e), b0.contiguous())                                     # [N, NW] per ray
+            h1 = G(xb, W0x)
+            _lib.check(lib.ucn_bias_relu(h1.data_ptr(), pr0.data_ptr(), N, S, NW, code, _lib.stream()))
+            dense_f32.forget(h1)                                                     # written through its raw pointer
+            pr1 = G(eb, R(W1e), b1.contiguous())
+            h2 = G(h1, W1h)
+            G(xb, W1x, flags=dense_f32.ACCUMULATE, out=h2)                           # accumulate in place: no copy
+            _lib.check(lib.ucn_bias_relu(h2.data_ptr(), pr1.data_ptr(), N, S, NW, code, _lib.stream()))
+            dense_f32.forget(h2)
+        else:
+            pr0 = torch.addmm(b0.to(dt), eb, W0e.t()).contiguous()                   # [N, NW] per ray
+            h1 = xb @ W0x.t()
+            _lib.check(lib.ucn_bias_relu(h1.data_ptr(), pr0.data_ptr(), N, S, NW, code, _lib.stream()))
+            pr1 = torch.addmm(b1.to(dt), eb, W1e.t()).contiguous()
+            h2 = (h1 @ W1h.t()).addmm_(xb, W1x.t())                                  # accumulate in place: no copy
+            _lib.check(lib.ucn_bias_relu(h2.data_ptr(), pr1.data_ptr(), N, S, NW, code, _lib.stream()))
+    return h2, xb, (xb, eb, h1, h2, W0x, W1h, W1x), (N, S, NB, NW, code, x.dtype, W0.dtype, b0.dtype, hip, enc.shape[1])
+
+
+def _colour_mlp_backward(saved, meta, g_h2, g_raw):
+    """_ColourMLP's backward: (d bottleneck operand, gW0, gb0, gW1, gb1); g_raw (or None) joins column 0 of the first."""
+    lib = _lib.load()
+    xb, eb, h1, h2, W0x, W1h, W1x = saved
+    N, S, NB, NW, code, x_dt, w_dt, b_dt, hip, E = meta
+    dt = xb.dtype
+    with torch.autocast("cuda", enabled=False):
+        g = g_h2.to(dt).contiguous()
+        d1 = torch.empty_like(g)
+        r1 = torch.empty(N, NW, device=g.device, dtype=dt)
+        _lib.check(lib.ucn_relu_backward_reduce(g.data_ptr(), h2.data_ptr(), d1.data_ptr(), r1.data_ptr(), N, S, NW, code,
+                                                _lib.stream()))
+        if hip:
+            # the same node on the hand-written fp32 kernels: dgrad = the forward kernel on the transposed weight; every
+            # weight gradient one pass of ucn_wgrad_f32 (fixed-order partial sums); both paths into x accumulate in one output
+            R, G, WG = dense_f32._rows, dense_f32.gemm, dense_f32.wgrad
+            d0 = G(d1, R(W1h.t()))                                                    # d h1, masked in place below
             r0 = torch.empty(N, NW, device=g.device, dtype=dt)
-            _lib.check(lib.ucn_relu_backward_reduce(d_h1.data_ptr(), h1.data_ptr(), d0.data_ptr(), r0.data_ptr(), N, S, NW, code,
+            _lib.check(lib.ucn_relu_backward_reduce(d0.data_ptr(), h1.data_ptr(), d0.data_ptr(), r0.data_ptr(), N, S, NW, code,
                                                     _lib.stream()))
-            gW0 = torch.cat([_wgrad(d0, xb), (r0.t() @ eb).float()], dim=1)
-            gW1 = torch.cat([_wgrad(d1, h1), _wgrad(d1, xb), (r1.t() @ eb).float()], dim=1)
-            gb0, gb1 = r0.float().sum(0), r1.float().sum(0)
-            gx = (d1 @ W1x).addmm_(d0, W0x)                                               # both paths into x in one output
+            dense_f32.forget(d0)                                                      # masked in place through its raw pointer
+            gW0 = torch.cat([WG(d0, xb)[0][:, :NB], WG(r0, eb)[0][:, :E]], dim=1)
+            gW1 = torch.cat([WG(d1, h1)[0], WG(d1, xb)[0][:, :NB], WG(r1, eb)[0][:, :E]], dim=1)
+            gb0, gb1 = r0.sum(0), r1.sum(0)
+            gx = G(d1, R(W1x[:, :NB].t()))
+            G(d0, R(W0x[:, :NB].t()), flags=dense_f32.ACCUMULATE, out=gx)
             if g_raw is not None:
-                gx[:, 0] += g_raw.reshape(-1).to(dt)                                      # the density head's column
-        return gx.to(x_dt), None, gW0.to(w_dt), gb0.to(b_dt), gW1.to(w_dt), gb1.to(b_dt), None, None
+                gx[:, 0] += g_raw.reshape(-1)
+            return gx[:, :NB].to(x_dt), gW0.to(w_dt), gb0.to(b_dt), gW1.to(w_dt), gb1.to(b_dt)
+        d_h1 = d1 @ W1h
+        d0 = d_h1                                                                     # masked in place
+        r0 = torch.empty(N, NW, device=g.device, dtype=dt)
+        _lib.check(lib.ucn_relu_backward_reduce(d_h1.data_ptr(), h1.data_ptr(), d0.data_ptr(), r0.data_ptr(), N, S, NW, code,
+                                                _lib.stream()))
+        gW0 = torch.cat([_wgrad(d0, xb), (r0.t() @ eb).float()], dim=1)
+        gW1 = torch.cat([_wgrad(d1, h1), _wgrad(d1, xb), (r1.t() @ eb).float()], dim=1)
+        gb0, gb1 = r0.float().sum(0), r1.float().sum(0)
+        gx = (d1 @ W1x).addmm_(d0, W0x)                                               # both paths into x in one output
+        if g_raw is not None:
+            gx[:, 0] += g_raw.reshape(-1).to(dt)                                      # the density head's column
+    return gx.to(x_dt), gW0.to(w_dt), gb0.to(b_dt), gW1.to(w_dt), gb1.to(b_dt)
+
+
+class _ColourMLPGlo(torch.autograd.Function):
+    """_ColourMLP with the GLO appearance modulation of the bottleneck (models.py:606-614) in front of it:
+
+        x' = x * a[ray] + b[ray],   a = exp(scale), b = shift  (float32 [N, NB], from the per-ray GLO MLP)
+
+    x' replaces x in both colour layers (skip input included); the raw density stays column 0 of the UNmodulated x
+    (models.py:508).  Forward and backward of the modulation are the HIP kernels ucn_ray_film / ucn_ray_film_backward; the
+    backward hands d a = sum_s d x' * x and d b = sum_s d x' (float32 [N, NB]) to ordinary autograd (exp, the GLO MLP,
+    glo_vecs).  The per-ray scale is why this is not the composed / fused route: those fold the bottleneck layer into the
+    colour layers' weights, which a per-ray diagonal between them breaks."""
+
+    @staticmethod
+    def forward(ctx, x, a, b, enc, W0, b0, W1, b1, N, S):
+        a, b = a.float().contiguous(), b.float().contiguous()
+        h2, _, saved, meta = _colour_mlp_forward(x, enc, W0, b0, W1, b1, N, S, film=(a, b))
+        xb = x.to(saved[0].dtype).contiguous()                                   # the unmodulated bottleneck, as the film read it
+        ctx.save_for_backward(xb, a, *saved)
+        ctx.meta = meta
+        return h2, xb[:, 0].clone()
+
+    @staticmethod
+    def backward(ctx, g_h2, g_raw):
+        lib = _lib.load()
+        xb, a, *saved = ctx.saved_tensors
+        N, S, NB, NW, code, x_dt, w_dt, b_dt, hip, E = ctx.meta
+        gy, gW0, gb0, gW1, gb1 = _colour_mlp_backward(saved, ctx.meta, g_h2, None)
+        with torch.autocast("cuda", enabled=False):
+            gy = gy.to(xb.dtype).contiguous()
+            gx = torch.empty_like(xb)
+            ga = torch.empty(N, NB, device=xb.device)
+            gb = torch.empty(N, NB, device=xb.device)
+            _lib.check(lib.ucn_ray_film_backward(gy.data_ptr(), xb.data_ptr(), a.data_ptr(), gx.data_ptr(), ga.data_ptr(), gb.data_ptr(),
+                                                 N, S, NB, code, _lib.stream()))
+            if g_raw is not None:
+                gx[:, 0] += g_raw.reshape(-1).to(gx.dtype)                         # the density head's column
+        return gx.to(x_dt), ga, gb, None, gW0, gb0, gW1, gb1, None, None
 
 
 def _colour_forward(h0, A0, pr0, W1h, A1, pr1, Wr, br, S):
@@ -843,15 +899,19 @@ def _fusable_heads(mlp, feat):
             and mlp.net_width_viewdirs == 256 and mlp.rgb_layer.out_features == 3)
 
 
-def field_heads(mlp, feat, viewdirs, N, S, chan=None):
+def field_heads(mlp, feat, viewdirs, N, S, chan=None, glo=None):
     """models.py:507-674 on [N*S, F] features: density MLP, softplus, colour MLP (torch GEMMs).
+
+    glo = (a, b), float32 [N, bottleneck] (MLP.glo_affine): the GLO modulation of the bottleneck, per ray.  It takes the
+    uncomposed route (_ColourMLPGlo); the fused / composed routes fold the bottleneck layer into the colour layers and are
+    only taken without it.
 
     The reference concatenates [bottleneck, dir_enc] (and [h, bottleneck, dir_enc] after the skip layer) per SAMPLE
     and multiplies by one weight.  The same product is formed here column block by column block: per-sample blocks
     as GEMMs that accumulate into one output, the per-RAY direction block (and the layer bias) as one small
     [N, 27] GEMM broadcast over the samples -- no [N*S, 283] / [N*S, 539] concatenations, 7 % fewer flops, and the
     bias / direction-weight gradients reduce over rays instead of samples."""
-    if _fusable_heads(mlp, feat) and os.environ.get("UCN_FUSED_HEADS", "1") == "1":
+    if glo is None and _fusable_heads(mlp, feat) and os.environ.get("UCN_FUSED_HEADS", "1") == "1":
         d0, d1, l0, l1, lr = mlp.density_layer[0], mlp.density_layer[2], mlp.lin_second_stage_0, mlp.lin_second_stage_1, mlp.rgb_layer
         density, rgb = _FusedHeads.apply(feat, view_encoding(viewdirs, mlp.deg_view), d0.weight, d0.bias, d1.weight, d1.bias,
                                          l0.weight, l0.bias, l1.weight, l1.bias, lr.weight, lr.bias, N, S,
@@ -861,7 +921,7 @@ def field_heads(mlp, feat, viewdirs, N, S, chan=None):
         l0, l1 = mlp.density_layer[0], mlp.density_layer[2]
         density = _PropHeads.apply(feat, l0.weight, l0.bias, l1.weight, l1.bias, mlp.density_bias, torch.is_autocast_enabled())
         return density.reshape(N, S), torch.zeros(N, S, 3, device=feat.device)
-    if (not mlp.disable_rgb and mlp.net_depth_viewdirs == 2 and mlp.skip_layer_dir == 0 and mlp.net_width_viewdirs % 8 == 0
+    if (glo is None and not mlp.disable_rgb and mlp.net_depth_viewdirs == 2 and mlp.skip_layer_dir == 0 and mlp.net_width_viewdirs % 8 == 0
             and dense_f32.usable(feat, mlp.density_layer[0].weight) and not dense_f32.library_route()
             and os.environ.get("UCN_F32_COMPOSED", "1") == "1"):        # 0: the uncomposed _ColourMLP on the same kernels (A/B, cross-check)
         # the fp32 step on hand-written kernels, the bottleneck composed into the colour layers (_ColourMLPComposed)
@@ -893,10 +953,15 @@ def field_heads(mlp, feat, viewdirs, N, S, chan=None):
     enc = view_encoding(viewdirs, mlp.deg_view)                                                  # [N, 27], per ray
     if mlp.net_depth_viewdirs == 2 and mlp.skip_layer_dir == 0 and mlp.net_width_viewdirs % 8 == 0:
         l0, l1 = mlp.lin_second_stage_0, mlp.lin_second_stage_1                                  # the reference's topology
-        h, raw = _ColourMLP.apply(x, enc, l0.weight, l0.bias, l1.weight, l1.bias, N, S)
+        if glo is not None:
+            h, raw = _ColourMLPGlo.apply(x, glo[0], glo[1], enc, l0.weight, l0.bias, l1.weight, l1.bias, N, S)
+        else:
+            h, raw = _ColourMLP.apply(x, enc, l0.weight, l0.bias, l1.weight, l1.bias, N, S)
         density = F.softplus(raw.reshape(N, S) + mlp.density_bias)
         rgb = torch.sigmoid(mlp.rgb_premultiplier * tall_linear(mlp.rgb_layer, h).reshape(N, S, -1) + mlp.rgb_bias)
         return density, rgb * (1 + 2 * mlp.rgb_padding) - mlp.rgb_padding
+    if glo is not None:
+        raise NotImplementedError("GLO modulation needs the reference's colour topology (net_depth_viewdirs = 2, skip_layer_dir = 0)")
     density = F.softplus(x.reshape(N, S, -1)[..., 0] + mlp.density_bias)
     per_sample, skip, with_enc = [x], [x], True            # column blocks of the next layer's input, in cat order
     for i in range(mlp.net_depth_viewdirs):
@@ -1357,10 +1422,12 @@ def brightness_forward(bc, idx, which="latent_code"):
     return run(codes)[idx]
 
 
-def march_train(model, rand, batch, train_frac, compute_extras, eval_camidx):
-    """Model.forward with an autograd graph (ref models.py:97-365)."""
+def march_train(model, rand, batch, train_frac, compute_extras, eval_camidx, glo_vec=None):
+    """Model.forward with an autograd graph (ref models.py:97-365).  glo_vec [N, num_glo_features] (or None): the NeRF level's
+    per-ray GLO codes (models.py:118-127); the proposal levels get none (models.py:226)."""
     from .models import _f32, _u_table
     lib = _lib.load()
+    model.last_march_route = 'train_graph'
     origins = batch['origins']
     _lib.require_device(origins, "batch['origins']")
     dev = origins.device
@@ -1432,7 +1499,8 @@ def march_train(model, rand, batch, train_frac, compute_extras, eval_camidx):
         chan = _GradChannel()                        # `feat` has exactly one consumer, the heads below: the two nodes may agree on its gradient's layout
         feat, coord, tmean = _FieldFeatures.apply(mlp.encoder.embeddings, mlp, geom, N, S, model.std_scale,
                                                   model.levels_per_block, half_table, chan)
-        density, rgbs = field_heads(mlp, feat, vd, N, S, chan)
+        glo = None if (is_prop or glo_vec is None) else mlp.glo_affine(glo_vec.reshape(N, -1))
+        density, rgbs = field_heads(mlp, feat, vd, N, S, chan, glo)
         if getattr(cfg, 'brightness_correction', False):              # models.py:233-235 (gated on this flag)
             rgbs, density = GradientScaler.apply(rgbs, density, tmean)
         weights, c_rgb, c_depth, c_acc = _Composite.apply(density, rgbs, sdist, near, far, d,
