@@ -112,6 +112,26 @@ int ucn_resample(const float *sdist_prev /*[N,n_prev+1]*/, const float *weights_
                  const float *u_table, const float *jitter, uint32_t jitter_cols, float max_jitter,
                  uint32_t N, uint32_t S, float *sdist_out /*[N,S+1]*/, ucn_stream_t stream);
 
+/* ref: coord.py:137-177 construct_ray_warps + models.py:130,208 (Model.raydist_fn, Model.power_lambda): the metric
+ * fenceposts of one level, tdist = fn_inv(sdist * fn(far) + (1 - sdist) * fn(near)) per ray, in fp32 in the reference's
+ * operation order (csrc/raydist.h).  S1 = fenceposts per ray (samples + 1); lam is read by UCN_RAYDIST_POWER only.
+ * The curves (fn | fn_inv):
+ *   IDENTITY    raydist_fn None                    x | y  -- exactly the march kernels' inline s * far + (1 - s) * near
+ *   PIECEWISE   'piecewise' (coord.py:156-159)      x < 1 ? x/2 : 1 - 1/(2x) | y < 1/2 ? 2y : 1/(2(1-y))
+ *   POWER       'power_transformation' (:160-162)  power_transformation(2x, lam) | inv_power_transformation(y, lam) / 2
+ *   RECIPROCAL, LOG, EXP, SQRT, SQUARE             the gin-bound torch callables (configs.py:13-19) and their
+ *                                                  inv_mapping partners (coord.py:164-172) */
+#define UCN_RAYDIST_IDENTITY 0
+#define UCN_RAYDIST_PIECEWISE 1
+#define UCN_RAYDIST_POWER 2
+#define UCN_RAYDIST_RECIPROCAL 3
+#define UCN_RAYDIST_LOG 4
+#define UCN_RAYDIST_EXP 5
+#define UCN_RAYDIST_SQRT 6
+#define UCN_RAYDIST_SQUARE 7
+int ucn_s_to_t(const float *sdist /*[N,S1]*/, const float *near_ /*[N]*/, const float *far_ /*[N]*/, uint32_t N,
+               uint32_t S1, int curve, float lam, float *tdist_out /*[N,S1]*/, ucn_stream_t stream);
+
 /* ref: render.py:139-146 -- the two cone cross-section axes from cam_dirs x rand_vec. */
 int ucn_cone_basis(const float *cam_dirs /*[N,3]*/, const float *rand_vec /*[N,3]*/, uint32_t N,
                    float *basis_out /*[N,6] = e1,e2*/, ucn_stream_t stream);
@@ -189,6 +209,19 @@ int ucn_march_features_backward(const ucn_field_t *f, const float *sdist, const 
                                                    algorithm then re-derives the geometry in every workgroup and
                                                    cannot compact its work (several times slower)*/,
                                 ucn_stream_t stream);
+/* The same two calls on METRIC fenceposts: tdist [N,S+1] from ucn_s_to_t (a warped Model.raydist_fn, models.py:208-214)
+ * in place of sdist / near / far; every other argument as above.  With the identity curve's tdist the results are
+ * bit-identical to ucn_march_features / ucn_march_features_backward. */
+int ucn_march_features_tdist(const ucn_field_t *f, const float *tdist /*[N,S+1]*/, const float *origins,
+                             const float *directions, const float *basis, const float *radii, const float *flip,
+                             const float *spin, float std_scale, uint32_t N, uint32_t S, uint32_t levels_per_block,
+                             int sample_major, float *features_out, float *coord_out, float *tmean_out,
+                             ucn_stream_t stream);
+int ucn_march_features_backward_tdist(const ucn_field_t *f, const float *tdist, const float *origins,
+                                      const float *directions, const float *basis, const float *radii, const float *flip,
+                                      const float *spin, float std_scale, uint32_t N, uint32_t S,
+                                      uint32_t levels_per_block, int sample_major, const float *grad_features,
+                                      float *grad_embeddings, float *workspace, ucn_stream_t stream);
 uint64_t ucn_march_features_backward_ws_floats(const ucn_field_t *f, uint32_t N, uint32_t S);
 /* ABI 26: 1 if that call (levels_per_block = 0, with its workspace) runs the compacted row-block kernel under float AND under
  * fixed-point rows -- the only route that accepts sample_major = 4; 0 where it would fall back (more than 512 row blocks in a level,
@@ -204,6 +237,10 @@ int ucn_march_features_backward_row_blocks(const ucn_field_t *f, uint32_t N, uin
 int ucn_cast_probe(const float *sdist, const float *near_, const float *far_, const float *origins,
                    const float *directions, const float *basis, const float *radii, const float *flip /*|NULL*/,
                    const float *spin /*|NULL*/, float std_scale, uint32_t N, uint32_t S, float *out, ucn_stream_t stream);
+/* ... on metric fenceposts tdist [N,S+1] (render.py:94 cast_rays(tdist, ...) after models.py:208 s_to_t). */
+int ucn_cast_probe_tdist(const float *tdist, const float *origins, const float *directions, const float *basis,
+                         const float *radii, const float *flip /*|NULL*/, const float *spin /*|NULL*/, float std_scale,
+                         uint32_t N, uint32_t S, float *out, ucn_stream_t stream);
 /* coord.py:60-72 contract_mean_std through the kernels' own device function: means [B,3], stds [B] ->
  * contracted mean / 2 [B,3], contracted std / 2 [B]. */
 int ucn_contract_probe(const float *means, const float *stds, uint32_t B, float *out_mean, float *out_std,
@@ -258,6 +295,12 @@ int ucn_composite(const float *density /*[N,S]*/, const float *rgbs /*[N,S,3]|NU
                   const float *directions, float bg_intensity, int opaque_background, uint32_t N,
                   uint32_t S, float *weights_out /*[N,S]*/, float *out_main, float *out_extras,
                   ucn_stream_t stream);
+/* ... on metric fenceposts tdist [N,S+1] (render.py:155-244 with models.py:208's warped tdist).  far_ stays the batch's
+ * metric far: the percentile CDF's last fencepost is t_far = batch['far'] (render.py:234, models.py:275-282). */
+int ucn_composite_tdist(const float *density, const float *rgbs /*|NULL*/, const float *tdist /*[N,S+1]*/,
+                        const float *far_, const float *directions, float bg_intensity, int opaque_background,
+                        uint32_t N, uint32_t S, float *weights_out, float *out_main, float *out_extras,
+                        ucn_stream_t stream);
 
 /* Backward of ucn_composite's differentiable outputs w.r.t. density and rgbs: what autograd derives from
  * render.py:155-174 + :203-216 in the reference's training step (train.py:165-221).  g_weights [N,S]|NULL is the
@@ -268,6 +311,11 @@ int ucn_composite_backward(const float *density, const float *rgbs, const float 
                            int opaque_background, uint32_t N, uint32_t S, const float *g_weights,
                            const float *g_main, float *g_density /*[N,S]*/, float *g_rgbs /*[N,S,3]|NULL*/,
                            ucn_stream_t stream);
+/* ... on metric fenceposts tdist [N,S+1] (ucn_composite_tdist's backward). */
+int ucn_composite_backward_tdist(const float *density, const float *rgbs, const float *tdist /*[N,S+1]*/,
+                                 const float *directions, float bg_intensity, int opaque_background, uint32_t N,
+                                 uint32_t S, const float *g_weights, const float *g_main, float *g_density,
+                                 float *g_rgbs, ucn_stream_t stream);
 
 /* ------------------------------------------------- training-side reductions + optimiser
  * ucn_adam_step: torch.optim.Adam (amsgrad = False, weight_decay = 0; what train_utils.py:347-366 builds) on one

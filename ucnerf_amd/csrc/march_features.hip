@@ -28,6 +28,7 @@
 //     for given positions -- stay bit-identical to the oracle.
 #include "ucn_common.h"
 #include "wave_dpp.h"
+#include "raydist.h"
 #include <type_traits>
 
 namespace {
@@ -39,6 +40,8 @@ struct HexPattern {
     float cj[6];      // 3/sqrt(7) * (2j/5 - 1)  (render.py:116)
 };
 
+// sdist: normalised fenceposts [N,S+1] of the identity curve, read with near_ / far_; in the kernels' TD = true variants
+// it holds metric fenceposts (ucn_s_to_t's tdist of a warped Model.raydist_fn) and near_ / far_ are unused.
 struct RayInputs {
     const float *sdist, *near_, *far_, *origins, *dirs, *basis, *radii, *flip, *spin;
 };
@@ -739,13 +742,14 @@ __device__ __forceinline__ void contract_to_unit(float x, float y, float z, floa
 
 // The six multisample Gaussians of sample (ray, s): render.py:108-152 then contract_to_unit.
 // Shared by the forward and the backward kernel (the backward recomputes it instead of reading back
-// 6x4 floats per sample).
+// 6x4 floats per sample).  TD: in.sdist holds metric fenceposts (see RayInputs).
+template <bool TD = false>
 __device__ __forceinline__ void cast_sample(const RayInputs &in, const HexPattern &hx, float std_scale, uint32_t ray,
                                             uint32_t s, uint32_t S, float (&u)[6][3], float (&rs)[6],
                                             float (&csum)[3], float &tsum, float *probe = nullptr) {
-    const float nr = in.near_[ray], fr = in.far_[ray];
+    const float nr = TD ? 0.0f : in.near_[ray], fr = TD ? 0.0f : in.far_[ray];
     const float s0 = in.sdist[(size_t)ray * (S + 1) + s], s1 = in.sdist[(size_t)ray * (S + 1) + s + 1];
-    const float t0 = s0 * fr + (1.0f - s0) * nr, t1 = s1 * fr + (1.0f - s1) * nr;
+    const float t0 = TD ? s0 : s0 * fr + (1.0f - s0) * nr, t1 = TD ? s1 : s1 * fr + (1.0f - s1) * nr;
     const float rad = in.radii[ray];
     const float *bp = in.basis + (size_t)ray * 6;
     const float e1x = bp[0], e1y = bp[1], e1z = bp[2], e2x = bp[3], e2y = bp[4], e2z = bp[5];
@@ -810,6 +814,7 @@ __device__ __forceinline__ void cast_sample(const RayInputs &in, const HexPatter
 
 // Introspection for the parity tests: the product's own cast_sample / contract_to_unit, results
 // written out instead of consumed.
+template <bool TD = false>
 __global__ __launch_bounds__(256) void k_cast_probe(RayInputs in, HexPattern hx, float std_scale, uint32_t N, uint32_t S,
                                                     float *__restrict__ out) {
     const size_t B = (size_t)N * S;
@@ -817,7 +822,7 @@ __global__ __launch_bounds__(256) void k_cast_probe(RayInputs in, HexPattern hx,
     if (b >= B) return;
     const uint32_t ray = (uint32_t)(b / S), s = (uint32_t)(b - (size_t)ray * S);
     float u[6][3], rs[6], csum[3], tsum;
-    cast_sample(in, hx, std_scale, ray, s, S, u, rs, csum, tsum, out + b * 6 * UCN_CAST_PROBE_FLOATS);
+    cast_sample<TD>(in, hx, std_scale, ray, s, S, u, rs, csum, tsum, out + b * 6 * UCN_CAST_PROBE_FLOATS);
 }
 
 __global__ __launch_bounds__(256) void k_contract_probe(const float *__restrict__ means, const float *__restrict__ stds,
@@ -861,11 +866,12 @@ static LevelGroups make_groups(const UcnLevels &lv, uint32_t levels_per_block) {
 // FEW_LEVELS is a NAME TAG only (same code): grids of <= 8 levels (the proposal fields: L = 6) and of more (the NeRF field:
 // L = 16 / 10) get distinct kernel names, so that a rocprofv3 --stats summary separates the proposal-level from the
 // NeRF-level launches without subtracting one from the other.
-template <uint32_t C, uint32_t TPB, typename TT = float, bool FEW_LEVELS = false>
-__global__ __launch_bounds__(TPB) void k_march_features(UcnLevels lvls, const TT *__restrict__ table, RayInputs in,
-                                                        HexPattern hx, float std_scale, uint32_t N, uint32_t S,
-                                                        LevelGroups grp, int layout, float *__restrict__ features,
-                                                        float *__restrict__ coord_out, float *__restrict__ tmean_out) {
+template <uint32_t C, uint32_t TPB, typename TT, bool TD>
+__device__ __forceinline__ void march_features_body(const UcnLevels &lvls, const TT *__restrict__ table, const RayInputs &in,
+                                                    const HexPattern &hx, float std_scale, uint32_t N, uint32_t S,
+                                                    const LevelGroups &grp, int layout,
+                                                    float *__restrict__ features, float *__restrict__ coord_out,
+                                                    float *__restrict__ tmean_out) {
     // co-resident shape (512 threads: launched beside an MLP workgroup on the same CU): a SIMD does not overlap VALU
     // with MFMA (tools/mfma_valu_bench.hip), so at equal priority every VALU instruction of this kernel would queue behind
     // one of the MLP wave's 32-cycle MFMAs.  With the higher priority the gather waves issue their bursts back to back and
@@ -881,7 +887,7 @@ __global__ __launch_bounds__(TPB) void k_march_features(UcnLevels lvls, const TT
     if ((layout & 3) == 2) { s = (uint32_t)(b / N); ray = (uint32_t)(b - (size_t)s * N); }
     else { ray = (uint32_t)(b / S); s = (uint32_t)(b - (size_t)ray * S); }
     float u[6][3], rs[6], csum[3], tsum;
-    cast_sample(in, hx, std_scale, ray, s, S, u, rs, csum, tsum);
+    cast_sample<TD>(in, hx, std_scale, ray, s, S, u, rs, csum, tsum);
     const uint32_t lvl0 = grp.lo[blockIdx.y], lvl1 = grp.lo[blockIdx.y + 1];
     const bool full_wave = __ballot(true) == ~0ull;                  // the lane-paired fetch trades rows between lanes i and i + 32
     const uint32_t lp_min = (layout & 0x20) ? kSharedCellMaxRes : kLanePairMinRes;     // 0x20: UCN_RAYS_INCOHERENT (private bit)
@@ -896,10 +902,28 @@ __global__ __launch_bounds__(TPB) void k_march_features(UcnLevels lvls, const TT
     }
 }
 
+template <uint32_t C, uint32_t TPB, typename TT = float, bool FEW_LEVELS = false>
+__global__ __launch_bounds__(TPB) void k_march_features(UcnLevels lvls, const TT *__restrict__ table, RayInputs in,
+                                                        HexPattern hx, float std_scale, uint32_t N, uint32_t S,
+                                                        LevelGroups grp, int layout, float *__restrict__ features,
+                                                        float *__restrict__ coord_out, float *__restrict__ tmean_out) {
+    march_features_body<C, TPB, TT, false>(lvls, table, in, hx, std_scale, N, S, grp, layout, features, coord_out, tmean_out);
+}
+
+// The same on metric fenceposts (a warped Model.raydist_fn): a kernel of its own NAME rather than a trailing TD argument of
+// k_march_features, whose last template argument (FEW_LEVELS) is how bench.py tells the NeRF-level launches from the others
+template <uint32_t C, uint32_t TPB, typename TT = float, bool FEW_LEVELS = false>
+__global__ __launch_bounds__(TPB) void k_march_features_td(UcnLevels lvls, const TT *__restrict__ table, RayInputs in,
+                                                           HexPattern hx, float std_scale, uint32_t N, uint32_t S,
+                                                           LevelGroups grp, int layout, float *__restrict__ features,
+                                                           float *__restrict__ coord_out, float *__restrict__ tmean_out) {
+    march_features_body<C, TPB, TT, true>(lvls, table, in, hx, std_scale, N, S, grp, layout, features, coord_out, tmean_out);
+}
+
 // d(loss)/d(table) of k_march_features.  (means/stds carry no gradient: coord.track_linearize is
 // @torch.no_grad, coord.py:75, and sdist is detached, models.py:204-205.)  fp32 atomics in L2, like
 // kernel_grid_backward (gridencoder.cu:336).
-template <uint32_t C>
+template <uint32_t C, bool TD = false>
 __global__ __launch_bounds__(256) void k_march_features_bwd(UcnLevels lvls, float *__restrict__ grad_table, RayInputs in,
                                                             HexPattern hx, float std_scale, uint32_t N, uint32_t S,
                                                             uint32_t lpb, int layout,
@@ -909,7 +933,7 @@ __global__ __launch_bounds__(256) void k_march_features_bwd(UcnLevels lvls, floa
     if (b >= B) return;
     const uint32_t ray = (uint32_t)(b / S), s = (uint32_t)(b - (size_t)ray * S);
     float u[6][3], rs[6], csum[3], tsum;
-    cast_sample(in, hx, std_scale, ray, s, S, u, rs, csum, tsum);
+    cast_sample<TD>(in, hx, std_scale, ray, s, S, u, rs, csum, tsum);
     const uint32_t lvl0 = blockIdx.y * lpb;
     const uint32_t lvl1 = lvl0 + lpb < lvls.L ? lvl0 + lpb : lvls.L;
     featurise_bwd<C>(lvls, grad_table, lvl0, lvl1, u, rs, 6, B, b, grad_features, layout == 1);
@@ -925,6 +949,7 @@ __global__ __launch_bounds__(256) void k_march_features_bwd(UcnLevels lvls, floa
 // The six contracted multisample positions and damping arguments of every sample, as [N*S][6] float4
 // {x, y, z, std argument} (one 16-byte load per point for the compacted kernel's scattered items): written once
 // per backward call, read by every (level, row block) workgroup.
+template <bool TD = false>
 __global__ __launch_bounds__(256) void k_cast_cache(RayInputs in, HexPattern hx, float std_scale, uint32_t N, uint32_t S,
                                                     float *__restrict__ geom) {
     const size_t B = (size_t)N * S;
@@ -932,7 +957,7 @@ __global__ __launch_bounds__(256) void k_cast_cache(RayInputs in, HexPattern hx,
     if (b >= B) return;
     const uint32_t ray = (uint32_t)(b / S), s = (uint32_t)(b - (size_t)ray * S);
     float u[6][3], rs[6], csum[3], tsum;
-    cast_sample(in, hx, std_scale, ray, s, S, u, rs, csum, tsum);
+    cast_sample<TD>(in, hx, std_scale, ray, s, S, u, rs, csum, tsum);
 #pragma unroll
     for (uint32_t j = 0; j < 6; j++) {
         reinterpret_cast<float4 *>(geom)[b * 6 + j] = make_float4(u[j][0], u[j][1], u[j][2], rs[j]);
@@ -1082,6 +1107,7 @@ __device__ __forceinline__ uint32_t point_block_mask(const UcnLevel &lv, uint32_
 }
 
 // geometry planes + block masks of every sample, once per backward call
+template <bool TD = false>
 __global__ __launch_bounds__(256, 1) void k_cast_cache_masks(UcnLevels lvls, RayInputs in, HexPattern hx, float std_scale,
                                                           uint32_t N, uint32_t S, MaskPlan plan,
                                                           const float *__restrict__ grad_features, GradStrides gs, uint32_t C,
@@ -1103,7 +1129,7 @@ __global__ __launch_bounds__(256, 1) void k_cast_cache_masks(UcnLevels lvls, Ray
     const size_t bb = valid ? b : B - 1;                  // lanes past the end recompute the last sample and store nothing
     const uint32_t ray = (uint32_t)(bb / S), s = (uint32_t)(bb - (size_t)ray * S);
     float u[6][3], rs[6], csum[3], tsum;
-    cast_sample(in, hx, std_scale, ray, s, S, u, rs, csum, tsum);
+    cast_sample<TD>(in, hx, std_scale, ray, s, S, u, rs, csum, tsum);
     if (valid) {
 #pragma unroll
         for (uint32_t j = 0; j < 6; j++) {
@@ -1357,7 +1383,7 @@ __device__ __forceinline__ void point_scatter_block(const UcnLevel &lv, A *__res
     }
 }
 
-template <uint32_t C>
+template <uint32_t C, bool TD = false>
 __global__ __launch_bounds__(1024) void k_march_features_bwd_blk(UcnLevels lvls, float *__restrict__ grad_table,
                                                                  RayInputs in, HexPattern hx, float std_scale, uint32_t N,
                                                                  uint32_t S, GradStrides gs, uint32_t rpb,
@@ -1399,7 +1425,7 @@ __global__ __launch_bounds__(1024) void k_march_features_bwd_blk(UcnLevels lvls,
         } else {
             const uint32_t ray = (uint32_t)(b / S), s = (uint32_t)(b - (size_t)ray * S);
             float csum[3], tsum;
-            cast_sample(in, hx, std_scale, ray, s, S, u, rs, csum, tsum);
+            cast_sample<TD>(in, hx, std_scale, ray, s, S, u, rs, csum, tsum);
         }
         if (lv.hashed) {
             if (lv.mask && lv.resolution <= 2048u) level_scatter_block<C, true, true, true>(lv, s_acc, row_lo, nrows, u, rs, gout);
@@ -2057,14 +2083,13 @@ int field_levels(const ucn_field_t *f, UcnLevels *lv) {
 
 }  // namespace
 
-extern "C" int ucn_march_features(const ucn_field_t *f, const float *sdist, const float *near_, const float *far_,
-                                  const float *origins, const float *directions, const float *basis,
-                                  const float *radii, const float *flip, const float *spin, float std_scale,
-                                  uint32_t N, uint32_t S, uint32_t levels_per_block, int layout,
-                                  float *features_out, float *coord_out, float *tmean_out, ucn_stream_t stream) {
-    UCN_REQUIRE(N == 0 || (sdist && near_ && far_ && origins && directions && basis && radii && features_out),
+template <bool TD>
+static int march_features_launch(const ucn_field_t *f, const RayInputs &in, float std_scale, uint32_t N, uint32_t S,
+                                 uint32_t levels_per_block, int layout, float *features_out, float *coord_out, float *tmean_out,
+                                 ucn_stream_t stream) {
+    UCN_REQUIRE(N == 0 || (in.sdist && (TD || (in.near_ && in.far_)) && in.origins && in.dirs && in.basis && in.radii && features_out),
                 "march_features: null pointer argument");
-    UCN_REQUIRE((flip == nullptr) == (spin == nullptr), "march_features: flip and spin come together");
+    UCN_REQUIRE((in.flip == nullptr) == (in.spin == nullptr), "march_features: flip and spin come together");
     const bool coresident = (layout & UCN_LAUNCH_CORESIDENT) != 0;
     const bool half_table = (layout & UCN_TABLE_F16) != 0;
     const bool out_bf16 = (layout & UCN_FEATURES_BF16) != 0;
@@ -2082,7 +2107,6 @@ extern "C" int ucn_march_features(const ucn_field_t *f, const float *sdist, cons
     const size_t B = (size_t)N * S;
     UCN_REQUIRE(B <= 0xFFFFFF00ull, "march_features: too many samples in one call (%zu)", B);
     const LevelGroups grp = make_groups(lv, levels_per_block);
-    const RayInputs in{sdist, near_, far_, origins, directions, basis, radii, flip, spin};
     const HexPattern hx = make_hex();
     hipStream_t st = (hipStream_t)stream;
     // co-resident shape: 512 threads = two waves per SIMD, 88 KiB of LDS reserved -> ONE such workgroup per CU, and
@@ -2091,18 +2115,23 @@ extern "C" int ucn_march_features(const ucn_field_t *f, const float *sdist, cons
     const uint32_t tpb = coresident ? 512u : 256u;
     const size_t lds = coresident ? 88u * 1024u : 0u;
     const dim3 grid(ucn_div_up(B, tpb), grp.n);
-#define UCN_MF2(CC, FEW)                                                                                                  \
+#define UCN_MF3(KF, CC, FEW)                                                                                                  \
     do {                                                                                                                  \
         if (half_table)                                                                                                   \
-            hipLaunchKernelGGL((k_march_features<CC, 256, _Float16, FEW>), grid, dim3(256), lds, st, lv,                  \
+            hipLaunchKernelGGL((KF<CC, 256, _Float16, FEW>), grid, dim3(256), lds, st, lv,                  \
                                reinterpret_cast<const _Float16 *>(f->embeddings), in, hx, std_scale, N, S, grp, layout,   \
                                features_out, coord_out, tmean_out);                                                       \
         else if (coresident)                                                                                              \
-            hipLaunchKernelGGL((k_march_features<CC, 512, float, FEW>), grid, dim3(512), lds, st, lv, f->embeddings, in, hx, std_scale, N, S, \
+            hipLaunchKernelGGL((KF<CC, 512, float, FEW>), grid, dim3(512), lds, st, lv, f->embeddings, in, hx, std_scale, N, S, \
                                grp, layout, features_out, coord_out, tmean_out);                                          \
         else                                                                                                              \
-            hipLaunchKernelGGL((k_march_features<CC, 256, float, FEW>), grid, dim3(256), lds, st, lv, f->embeddings, in, hx, std_scale, N, S, \
+            hipLaunchKernelGGL((KF<CC, 256, float, FEW>), grid, dim3(256), lds, st, lv, f->embeddings, in, hx, std_scale, N, S, \
                                grp, layout, features_out, coord_out, tmean_out);                                          \
+    } while (0)
+#define UCN_MF2(CC, FEW)                                                                                                  \
+    do {                                                                                                                  \
+        if constexpr (TD) UCN_MF3(k_march_features_td, CC, FEW);                                                          \
+        else UCN_MF3(k_march_features, CC, FEW);                                                                          \
     } while (0)
 #define UCN_MF(CC)                                                                                                        \
     do {                                                                                                                  \
@@ -2115,24 +2144,57 @@ extern "C" int ucn_march_features(const ucn_field_t *f, const float *sdist, cons
         case 4: UCN_MF(4); break;
         case 8: UCN_MF(8); break;
     }
+#undef UCN_MF3
 #undef UCN_MF2
 #undef UCN_MF
     UCN_LAUNCH_CHECK("march_features");
     return 0;
 }
 
-extern "C" int ucn_cast_probe(const float *sdist, const float *near_, const float *far_, const float *origins,
-                              const float *directions, const float *basis, const float *radii, const float *flip,
-                              const float *spin, float std_scale, uint32_t N, uint32_t S, float *out, ucn_stream_t stream) {
-    UCN_REQUIRE(N == 0 || (sdist && near_ && far_ && origins && directions && basis && radii && out),
-                "cast_probe: null pointer argument");
-    UCN_REQUIRE((flip == nullptr) == (spin == nullptr), "cast_probe: flip and spin come together");
-    if (N == 0 || S == 0) return 0;
+extern "C" int ucn_march_features(const ucn_field_t *f, const float *sdist, const float *near_, const float *far_,
+                                  const float *origins, const float *directions, const float *basis,
+                                  const float *radii, const float *flip, const float *spin, float std_scale,
+                                  uint32_t N, uint32_t S, uint32_t levels_per_block, int layout,
+                                  float *features_out, float *coord_out, float *tmean_out, ucn_stream_t stream) {
     const RayInputs in{sdist, near_, far_, origins, directions, basis, radii, flip, spin};
-    hipLaunchKernelGGL(k_cast_probe, dim3(ucn_div_up((size_t)N * S, 256)), dim3(256), 0, (hipStream_t)stream, in, make_hex(),
+    return march_features_launch<false>(f, in, std_scale, N, S, levels_per_block, layout, features_out, coord_out, tmean_out,
+                                        stream);
+}
+
+extern "C" int ucn_march_features_tdist(const ucn_field_t *f, const float *tdist, const float *origins,
+                                        const float *directions, const float *basis, const float *radii, const float *flip,
+                                        const float *spin, float std_scale, uint32_t N, uint32_t S, uint32_t levels_per_block,
+                                        int layout, float *features_out, float *coord_out, float *tmean_out,
+                                        ucn_stream_t stream) {
+    const RayInputs in{tdist, nullptr, nullptr, origins, directions, basis, radii, flip, spin};
+    return march_features_launch<true>(f, in, std_scale, N, S, levels_per_block, layout, features_out, coord_out, tmean_out,
+                                       stream);
+}
+
+template <bool TD>
+static int cast_probe_launch(const RayInputs &in, float std_scale, uint32_t N, uint32_t S, float *out, ucn_stream_t stream) {
+    UCN_REQUIRE(N == 0 || (in.sdist && (TD || (in.near_ && in.far_)) && in.origins && in.dirs && in.basis && in.radii && out),
+                "cast_probe: null pointer argument");
+    UCN_REQUIRE((in.flip == nullptr) == (in.spin == nullptr), "cast_probe: flip and spin come together");
+    if (N == 0 || S == 0) return 0;
+    hipLaunchKernelGGL(k_cast_probe<TD>, dim3(ucn_div_up((size_t)N * S, 256)), dim3(256), 0, (hipStream_t)stream, in, make_hex(),
                        std_scale, N, S, out);
     UCN_LAUNCH_CHECK("cast_probe");
     return 0;
+}
+
+extern "C" int ucn_cast_probe(const float *sdist, const float *near_, const float *far_, const float *origins,
+                              const float *directions, const float *basis, const float *radii, const float *flip,
+                              const float *spin, float std_scale, uint32_t N, uint32_t S, float *out, ucn_stream_t stream) {
+    return cast_probe_launch<false>(RayInputs{sdist, near_, far_, origins, directions, basis, radii, flip, spin}, std_scale, N, S,
+                                    out, stream);
+}
+
+extern "C" int ucn_cast_probe_tdist(const float *tdist, const float *origins, const float *directions, const float *basis,
+                                    const float *radii, const float *flip, const float *spin, float std_scale, uint32_t N,
+                                    uint32_t S, float *out, ucn_stream_t stream) {
+    return cast_probe_launch<true>(RayInputs{tdist, nullptr, nullptr, origins, directions, basis, radii, flip, spin}, std_scale, N,
+                                   S, out, stream);
 }
 
 extern "C" int ucn_contract_probe(const float *means, const float *stds, uint32_t B, float *out_mean, float *out_std,
@@ -2196,15 +2258,13 @@ extern "C" int ucn_march_features_backward_row_blocks(const ucn_field_t *f, uint
     return (B > 0 && bwd_row_block_plan(lv, B, false, &plan) && bwd_row_block_plan(lv, B, true, &plan)) ? 1 : 0;
 }
 
-extern "C" int ucn_march_features_backward(const ucn_field_t *f, const float *sdist, const float *near_, const float *far_,
-                                           const float *origins, const float *directions, const float *basis,
-                                           const float *radii, const float *flip, const float *spin, float std_scale,
-                                           uint32_t N, uint32_t S, uint32_t levels_per_block, int layout,
-                                           const float *grad_features, float *grad_embeddings, float *workspace,
-                                           ucn_stream_t stream) {
-    UCN_REQUIRE(sdist && near_ && far_ && origins && directions && basis && radii && grad_features && grad_embeddings,
-                "march_features_backward: null pointer argument");
-    UCN_REQUIRE((flip == nullptr) == (spin == nullptr), "march_features_backward: flip and spin come together");
+template <bool TD>
+static int march_features_backward_launch(const ucn_field_t *f, const RayInputs &in, float std_scale, uint32_t N, uint32_t S,
+                                          uint32_t levels_per_block, int layout, const float *grad_features,
+                                          float *grad_embeddings, float *workspace, ucn_stream_t stream) {
+    UCN_REQUIRE(in.sdist && (TD || (in.near_ && in.far_)) && in.origins && in.dirs && in.basis && in.radii && grad_features &&
+                grad_embeddings, "march_features_backward: null pointer argument");
+    UCN_REQUIRE((in.flip == nullptr) == (in.spin == nullptr), "march_features_backward: flip and spin come together");
     const bool want_fixed = (layout & UCN_BWD_FIXED_POINT) != 0;
     layout &= ~UCN_BWD_FIXED_POINT;
     const bool prediv = layout == 4;                     // level-major and already / 6: read in place
@@ -2219,7 +2279,6 @@ extern "C" int ucn_march_features_backward(const ucn_field_t *f, const float *sd
     // target: C = 1 and calls with 2^30 + 24 B >= 2^31 keep float rows
     const bool fixed = want_fixed && lv.C % 2u == 0u && B <= (1ull << 22);
     static_assert((1ull << 30) + 24ull * (1ull << 22) < (1ull << 31), "fixed-point row blocks: int32 headroom");
-    const RayInputs in{sdist, near_, far_, origins, directions, basis, radii, flip, spin};
     const HexPattern hx = make_hex();
     const GradStrides gs = grad_strides(layout, B, lv.L, lv.C);
     hipStream_t st = (hipStream_t)stream;
@@ -2246,7 +2305,7 @@ extern "C" int ucn_march_features_backward(const ucn_field_t *f, const float *sd
             float *glm = workspace + (24ull + plan.n_planes) * B;                               // level-major copy, / 6
             uint32_t *task_counter = reinterpret_cast<uint32_t *>(workspace + (24ull + plan.n_planes + (size_t)lv.L * lv.C) * B);
             float *l1_partial = reinterpret_cast<float *>(task_counter + 64);                   // [L][ceil(B / 256)] (fixed-point mode)
-            hipLaunchKernelGGL(k_cast_cache_masks, dim3(ucn_div_up(B, 256)), dim3(256), 0, st, lv, in, hx, std_scale, N, S, plan,
+            hipLaunchKernelGGL(k_cast_cache_masks<TD>, dim3(ucn_div_up(B, 256)), dim3(256), 0, st, lv, in, hx, std_scale, N, S, plan,
                                grad_features, gs, lv.C, workspace, masks, prediv ? nullptr : glm, task_counter, fixed ? l1_partial : nullptr);
             const float *glv = prediv ? grad_features : glm;                                    // [L][B][C], / 6
             const uint32_t cus = device_cu_count();
@@ -2274,9 +2333,9 @@ extern "C" int ucn_march_features_backward(const ucn_field_t *f, const float *sd
         UCN_REQUIRE(!prediv, "march_features_backward: layout 4 (pre-divided level-major gradient) is the compacted row-block kernel's input; this call would take a fallback");
         if (blocks <= 64u * lv.L) {
             if (workspace)
-                hipLaunchKernelGGL(k_cast_cache, dim3(ucn_div_up(B, 256)), dim3(256), 0, st, in, hx, std_scale, N, S, workspace);
+                hipLaunchKernelGGL(k_cast_cache<TD>, dim3(ucn_div_up(B, 256)), dim3(256), 0, st, in, hx, std_scale, N, S, workspace);
 #define UCN_MBB(CC)                                                                                              \
-    hipLaunchKernelGGL(k_march_features_bwd_blk<CC>, dim3(tasks), dim3(1024), (size_t)rpb * CC * 4, st, lv,      \
+    hipLaunchKernelGGL((k_march_features_bwd_blk<CC, TD>), dim3(tasks), dim3(1024), (size_t)rpb * CC * 4, st, lv,      \
                        grad_embeddings, in, hx, std_scale, N, S, gs, rpb, grad_features, workspace)
             switch (lv.C) {
                 case 1: UCN_MBB(1); break;
@@ -2294,7 +2353,7 @@ extern "C" int ucn_march_features_backward(const ucn_field_t *f, const float *sd
     UCN_REQUIRE(!prediv, "march_features_backward: layout 4 is a row-block layout (levels_per_block = 0 with a workspace)");
     const dim3 grid(ucn_div_up(B, 256), ucn_div_up(lv.L, levels_per_block));
 #define UCN_MB(CC)                                                                                                  \
-    hipLaunchKernelGGL(k_march_features_bwd<CC>, grid, dim3(256), 0, st, lv, grad_embeddings, in, hx, std_scale, N, \
+    hipLaunchKernelGGL((k_march_features_bwd<CC, TD>), grid, dim3(256), 0, st, lv, grad_embeddings, in, hx, std_scale, N, \
                        S, levels_per_block, layout, grad_features)
     switch (lv.C) {
         case 1: UCN_MB(1); break;
@@ -2305,6 +2364,27 @@ extern "C" int ucn_march_features_backward(const ucn_field_t *f, const float *sd
 #undef UCN_MB
     UCN_LAUNCH_CHECK("march_features_backward");
     return 0;
+}
+
+extern "C" int ucn_march_features_backward(const ucn_field_t *f, const float *sdist, const float *near_, const float *far_,
+                                           const float *origins, const float *directions, const float *basis,
+                                           const float *radii, const float *flip, const float *spin, float std_scale,
+                                           uint32_t N, uint32_t S, uint32_t levels_per_block, int layout,
+                                           const float *grad_features, float *grad_embeddings, float *workspace,
+                                           ucn_stream_t stream) {
+    const RayInputs in{sdist, near_, far_, origins, directions, basis, radii, flip, spin};
+    return march_features_backward_launch<false>(f, in, std_scale, N, S, levels_per_block, layout, grad_features, grad_embeddings,
+                                                 workspace, stream);
+}
+
+extern "C" int ucn_march_features_backward_tdist(const ucn_field_t *f, const float *tdist, const float *origins,
+                                                 const float *directions, const float *basis, const float *radii,
+                                                 const float *flip, const float *spin, float std_scale, uint32_t N, uint32_t S,
+                                                 uint32_t levels_per_block, int layout, const float *grad_features,
+                                                 float *grad_embeddings, float *workspace, ucn_stream_t stream) {
+    const RayInputs in{tdist, nullptr, nullptr, origins, directions, basis, radii, flip, spin};
+    return march_features_backward_launch<true>(f, in, std_scale, N, S, levels_per_block, layout, grad_features, grad_embeddings,
+                                                workspace, stream);
 }
 
 extern "C" int ucn_points_features(const ucn_field_t *f, const float *means, const float *stds, uint32_t B, uint32_t G,

@@ -12,6 +12,7 @@
 // lookups are ballots over the CDF held in LDS.
 #include "ucn_common.h"
 #include "wave_dpp.h"
+#include "raydist.h"
 
 namespace {
 
@@ -324,7 +325,9 @@ __device__ __forceinline__ float nan_to_num_inf(float v) {
 }
 
 // One wave64 per ray, 4 rays per workgroup.  Lane owns CH consecutive samples.
-template <int CH>
+// TD = false: `sdist` holds normalised fenceposts of the identity curve; TD = true: metric fenceposts (ucn_s_to_t's tdist),
+// near_ unused.  far_ is the batch's metric far either way (the percentile CDF's last fencepost, render.py:234).
+template <int CH, bool TD = false>
 __global__ __launch_bounds__(256) void k_composite(const float *__restrict__ density, const float *__restrict__ rgbs,
                                                    const float *__restrict__ sdist, const float *__restrict__ near_,
                                                    const float *__restrict__ far_, const float *__restrict__ dirs,
@@ -337,7 +340,7 @@ __global__ __launch_bounds__(256) void k_composite(const float *__restrict__ den
     const uint32_t ray_raw = blockIdx.x * 4u + wv;
     const bool live = ray_raw < N;                       // wave-uniform; dead waves still reach the barrier
     const uint32_t ray = live ? ray_raw : N - 1;
-    const float nr = near_[ray], fr = far_[ray];
+    const float nr = TD ? 0.0f : near_[ray], fr = far_[ray];
     const float dx = dirs[ray * 3 + 0], dy = dirs[ray * 3 + 1], dz = dirs[ray * 3 + 2];
     const float dnorm = sqrtf((dx * dx + dy * dy) + dz * dz);
     const float *sd = sdist + (size_t)ray * (S + 1);
@@ -348,8 +351,8 @@ __global__ __launch_bounds__(256) void k_composite(const float *__restrict__ den
         const uint32_t i = lane * CH + c;
         if (i < S) {
             const float s0 = sd[i], s1 = sd[i + 1];
-            tlo[c] = s0 * fr + (1.0f - s0) * nr;          // coord.py:176 with fn = identity
-            thi[c] = s1 * fr + (1.0f - s1) * nr;
+            tlo[c] = TD ? s0 : s0 * fr + (1.0f - s0) * nr;          // coord.py:176 with fn = identity (TD: tdist as given)
+            thi[c] = TD ? s1 : s1 * fr + (1.0f - s1) * nr;
             float td = density[(size_t)ray * S + i] * ((thi[c] - tlo[c]) * dnorm);
             if (opaque && i == S - 1) td = INFINITY;
             tau[c] = td;
@@ -390,8 +393,8 @@ __global__ __launch_bounds__(256) void k_composite(const float *__restrict__ den
     r = wave_sum(r); g = wave_sum(g); b = wave_sum(b);
     dnum = wave_sum(dnum);
     lnum = wave_sum(lnum);
-    const float t_first = sd[0] * fr + (1.0f - sd[0]) * nr;
-    const float t_last = sd[S] * fr + (1.0f - sd[S]) * nr;
+    const float t_first = TD ? sd[0] : sd[0] * fr + (1.0f - sd[0]) * nr;
+    const float t_last = TD ? sd[S] : sd[S] * fr + (1.0f - sd[S]) * nr;
     const float bg_w = fmaxf(1.0f - acc, 0.0f);
     const float denom = fmaxf(acc, UCN_EPS);
     float depth = fminf(fmaxf(nan_to_num_inf(dnum / denom), t_first), t_last);
@@ -446,7 +449,7 @@ __global__ __launch_bounds__(256) void k_composite(const float *__restrict__ den
 // (the suffix sum is a wave scan).  G collects the direct weight gradient (the losses on `weights`), rgb
 // (sum_i w_i c_i + bg * clamp_min(1 - acc, 0)), acc and depth (clip(nan_to_num(sum_i w_i tm_i / max(acc, eps))), 300
 // where acc < 0.6 -- constant there).
-template <int CH>
+template <int CH, bool TD = false>
 __global__ __launch_bounds__(256) void k_composite_bwd(const float *__restrict__ density, const float *__restrict__ rgbs,
                                                        const float *__restrict__ sdist, const float *__restrict__ near_,
                                                        const float *__restrict__ far_, const float *__restrict__ dirs,
@@ -456,7 +459,7 @@ __global__ __launch_bounds__(256) void k_composite_bwd(const float *__restrict__
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const uint32_t ray = blockIdx.x * 4u + wv;
     if (ray >= N) return;                                 // wave-uniform, no barriers below
-    const float nr = near_[ray], fr = far_[ray];
+    const float nr = TD ? 0.0f : near_[ray], fr = TD ? 0.0f : far_[ray];
     const float dx = dirs[ray * 3 + 0], dy = dirs[ray * 3 + 1], dz = dirs[ray * 3 + 2];
     const float dnorm = sqrtf((dx * dx + dy * dy) + dz * dz);
     const float *sd = sdist + (size_t)ray * (S + 1);
@@ -470,7 +473,7 @@ __global__ __launch_bounds__(256) void k_composite_bwd(const float *__restrict__
         tm[c] = scale[c] = tau[c] = 0.0f;
         if (i < S) {
             const float s0 = sd[i], s1 = sd[i + 1];
-            const float tlo = s0 * fr + (1.0f - s0) * nr, thi = s1 * fr + (1.0f - s1) * nr;
+            const float tlo = TD ? s0 : s0 * fr + (1.0f - s0) * nr, thi = TD ? s1 : s1 * fr + (1.0f - s1) * nr;
             tm[c] = 0.5f * (tlo + thi);
             scale[c] = (thi - tlo) * dnorm;
             float td = density[(size_t)ray * S + i] * scale[c];
@@ -497,7 +500,7 @@ __global__ __launch_bounds__(256) void k_composite_bwd(const float *__restrict__
     const float acc = wave_sum(lane_w);
     dnum = wave_sum(dnum);
     // depth = clip(nan_to_num(dnum / max(acc, eps)), t_0, t_S), overwritten by 300 where acc < 0.6
-    const float t_first = sd[0] * fr + (1.0f - sd[0]) * nr, t_last = sd[S] * fr + (1.0f - sd[S]) * nr;
+    const float t_first = TD ? sd[0] : sd[0] * fr + (1.0f - sd[0]) * nr, t_last = TD ? sd[S] : sd[S] * fr + (1.0f - sd[S]) * nr;
     const float denom = fmaxf(acc, UCN_EPS);
     const float draw = dnum / denom;
     const bool dlive = gdepth != 0.0f && !(acc < 0.6f) && draw == draw && fabsf(draw) != INFINITY && draw >= t_first &&
@@ -538,7 +541,37 @@ __global__ __launch_bounds__(256) void k_composite_bwd(const float *__restrict__
     }
 }
 
+// tdist = s_to_t(sdist) of every fencepost (coord.py:176).  One wave64 per ray, 4 rays per workgroup: the even lanes evaluate
+// fn(near), the odd ones fn(far) -- one curve evaluation per lane -- and the wave shares the two, so a fencepost costs one
+// inverse (one precise powf on the power curve) instead of three.  The lanes walk the ray's fenceposts (coalesced, 4 B read and
+// written per fencepost and level).
+__global__ __launch_bounds__(256) void k_s_to_t(const float *__restrict__ sdist, const float *__restrict__ near_,
+                                                const float *__restrict__ far_, uint32_t N, uint32_t S1, UcnRaydist rd,
+                                                float *__restrict__ tdist) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t ray = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (ray >= N) return;                                 // wave-uniform, no barriers below
+    const float nr = near_[ray], fr = far_[ray];
+    const float v = ucn_raydist_fwd(rd, (lane & 1u) ? fr : nr);
+    const float sn = __shfl(v, 0, 64), sf = __shfl(v, 1, 64);
+    const float *sd = sdist + (size_t)ray * S1;
+    float *td = tdist + (size_t)ray * S1;
+    for (uint32_t i = lane; i < S1; i += 64u) td[i] = ucn_raydist_s_to_t(rd, sd[i], nr, fr, sn, sf);
+}
+
 }  // namespace
+
+extern "C" int ucn_s_to_t(const float *sdist, const float *near_, const float *far_, uint32_t N, uint32_t S1, int curve,
+                          float lam, float *tdist_out, ucn_stream_t stream) {
+    UCN_REQUIRE(curve >= UCN_RAYDIST_IDENTITY && curve <= UCN_RAYDIST_SQUARE, "s_to_t: unknown ray-distance curve %d", curve);
+    UCN_REQUIRE(N == 0 || S1 == 0 || (sdist && near_ && far_ && tdist_out), "s_to_t: null pointer argument");
+    const size_t n = (size_t)N * S1;
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(k_s_to_t, dim3(ucn_div_up(N, 4)), dim3(256), 0, (hipStream_t)stream, sdist, near_, far_, N, S1,
+                       ucn_raydist_make(curve, (double)lam), tdist_out);
+    UCN_LAUNCH_CHECK("s_to_t");
+    return 0;
+}
 
 extern "C" int ucn_resample(const float *sdist_prev, const float *weights_prev, uint32_t n_prev, float dilation,
                             float anneal, float resample_padding, const float *u_table, const float *jitter,
@@ -574,17 +607,18 @@ extern "C" int ucn_cone_basis(const float *cam_dirs, const float *rand_vec, uint
     return 0;
 }
 
-extern "C" int ucn_composite(const float *density, const float *rgbs, const float *sdist, const float *near_,
-                             const float *far_, const float *directions, float bg_intensity, int opaque_background,
-                             uint32_t N, uint32_t S, float *weights_out, float *out_main, float *out_extras,
-                             ucn_stream_t stream) {
-    UCN_REQUIRE(N == 0 || (density && sdist && near_ && far_ && directions && weights_out && out_main), "composite: null pointer argument");
+template <bool TD>
+static int composite_launch(const float *density, const float *rgbs, const float *sdist, const float *near_, const float *far_,
+                            const float *directions, float bg_intensity, int opaque_background, uint32_t N, uint32_t S,
+                            float *weights_out, float *out_main, float *out_extras, ucn_stream_t stream) {
+    UCN_REQUIRE(N == 0 || (density && sdist && (TD || near_) && far_ && directions && weights_out && out_main),
+                "composite: null pointer argument");
     UCN_REQUIRE(S >= 1 && S <= 512, "composite: samples per ray must be in [1,512], got %u", S);
     if (N == 0) return 0;
     const dim3 grid(ucn_div_up(N, 4));
     hipStream_t st = (hipStream_t)stream;
-#define UCN_CP(CH)                                                                                               \
-    hipLaunchKernelGGL(k_composite<CH>, grid, dim3(256), 0, st, density, rgbs, sdist, near_, far_, directions,   \
+#define UCN_CP(CH)                                                                                                   \
+    hipLaunchKernelGGL((k_composite<CH, TD>), grid, dim3(256), 0, st, density, rgbs, sdist, near_, far_, directions, \
                        bg_intensity, opaque_background, N, S, weights_out, out_main, out_extras)
     if (S <= 64) UCN_CP(1);
     else if (S <= 128) UCN_CP(2);
@@ -593,6 +627,21 @@ extern "C" int ucn_composite(const float *density, const float *rgbs, const floa
 #undef UCN_CP
     UCN_LAUNCH_CHECK("composite");
     return 0;
+}
+
+extern "C" int ucn_composite(const float *density, const float *rgbs, const float *sdist, const float *near_,
+                             const float *far_, const float *directions, float bg_intensity, int opaque_background,
+                             uint32_t N, uint32_t S, float *weights_out, float *out_main, float *out_extras,
+                             ucn_stream_t stream) {
+    return composite_launch<false>(density, rgbs, sdist, near_, far_, directions, bg_intensity, opaque_background, N, S,
+                                   weights_out, out_main, out_extras, stream);
+}
+
+extern "C" int ucn_composite_tdist(const float *density, const float *rgbs, const float *tdist, const float *far_,
+                                   const float *directions, float bg_intensity, int opaque_background, uint32_t N, uint32_t S,
+                                   float *weights_out, float *out_main, float *out_extras, ucn_stream_t stream) {
+    return composite_launch<true>(density, rgbs, tdist, nullptr, far_, directions, bg_intensity, opaque_background, N, S,
+                                  weights_out, out_main, out_extras, stream);
 }
 
 namespace {
@@ -662,18 +711,20 @@ extern "C" int ucn_compact_alive(const float *weights, uint32_t N, uint32_t S, i
     return 0;
 }
 
-extern "C" int ucn_composite_backward(const float *density, const float *rgbs, const float *sdist, const float *near_,
-                                      const float *far_, const float *directions, float bg_intensity, int opaque_background,
-                                      uint32_t N, uint32_t S, const float *g_weights, const float *g_main,
-                                      float *g_density, float *g_rgbs, ucn_stream_t stream) {
-    UCN_REQUIRE(N == 0 || (density && sdist && near_ && far_ && directions && g_main && g_density), "composite_backward: null pointer argument");
+template <bool TD>
+static int composite_backward_launch(const float *density, const float *rgbs, const float *sdist, const float *near_,
+                                     const float *far_, const float *directions, float bg_intensity, int opaque_background,
+                                     uint32_t N, uint32_t S, const float *g_weights, const float *g_main, float *g_density,
+                                     float *g_rgbs, ucn_stream_t stream) {
+    UCN_REQUIRE(N == 0 || (density && sdist && (TD || (near_ && far_)) && directions && g_main && g_density),
+                "composite_backward: null pointer argument");
     UCN_REQUIRE((rgbs == nullptr) == (g_rgbs == nullptr), "composite_backward: rgbs and g_rgbs come together");
     UCN_REQUIRE(S >= 1 && S <= 512, "composite_backward: samples per ray must be in [1,512], got %u", S);
     if (N == 0) return 0;
     const dim3 grid(ucn_div_up(N, 4));
     hipStream_t st = (hipStream_t)stream;
-#define UCN_CB(CH)                                                                                                \
-    hipLaunchKernelGGL(k_composite_bwd<CH>, grid, dim3(256), 0, st, density, rgbs, sdist, near_, far_, directions, \
+#define UCN_CB(CH)                                                                                                     \
+    hipLaunchKernelGGL((k_composite_bwd<CH, TD>), grid, dim3(256), 0, st, density, rgbs, sdist, near_, far_, directions, \
                        bg_intensity, opaque_background, N, S, g_weights, g_main, g_density, g_rgbs)
     if (S <= 64) UCN_CB(1);
     else if (S <= 128) UCN_CB(2);
@@ -682,4 +733,20 @@ extern "C" int ucn_composite_backward(const float *density, const float *rgbs, c
 #undef UCN_CB
     UCN_LAUNCH_CHECK("composite_backward");
     return 0;
+}
+
+extern "C" int ucn_composite_backward(const float *density, const float *rgbs, const float *sdist, const float *near_,
+                                      const float *far_, const float *directions, float bg_intensity, int opaque_background,
+                                      uint32_t N, uint32_t S, const float *g_weights, const float *g_main,
+                                      float *g_density, float *g_rgbs, ucn_stream_t stream) {
+    return composite_backward_launch<false>(density, rgbs, sdist, near_, far_, directions, bg_intensity, opaque_background, N, S,
+                                            g_weights, g_main, g_density, g_rgbs, stream);
+}
+
+extern "C" int ucn_composite_backward_tdist(const float *density, const float *rgbs, const float *tdist,
+                                            const float *directions, float bg_intensity, int opaque_background, uint32_t N,
+                                            uint32_t S, const float *g_weights, const float *g_main, float *g_density,
+                                            float *g_rgbs, ucn_stream_t stream) {
+    return composite_backward_launch<true>(density, rgbs, tdist, nullptr, nullptr, directions, bg_intensity, opaque_background,
+                                           N, S, g_weights, g_main, g_density, g_rgbs, stream);
 }

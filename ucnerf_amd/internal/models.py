@@ -9,8 +9,9 @@ signature: a sampling level is five kernel launches on the caller's HIP stream
 composite) instead of ~300 eager ops, and nothing of size [N*S*6, .] is ever materialised.
 
 Supported configuration = the reference's shipped one (configs/waymo.gin): disable_density_normals,
-no reflections / diffuse / IDE, raydist_fn=None, plus GLO appearance codes (num_glo_features > 0; DESIGN.md
-"GLO").  Anything else raises at construction.
+no reflections / diffuse / IDE, plus GLO appearance codes (num_glo_features > 0; DESIGN.md "GLO") and every
+ray-distance curve of coord.construct_ray_warps (raydist_fn None, 'piecewise', 'power_transformation' or a gin-bound
+torch.reciprocal / log / exp / sqrt / square; DESIGN.md "Ray-distance curves").  Anything else raises at construction.
 In eval mode or with gradients disabled forward is the fused inference march; a model in training mode
 with gradients enabled routes to internal/train_graph.py (same kernels for resampling and featurisation, HIP
 backward for the tables and the dense layers' dgrad, autograd glue; `Model.march_route`).  Without the HIP library or a GPU every entry point raises.
@@ -74,6 +75,50 @@ def glo_fold(W0, b0, W1, b1, a, b):
 
 
 _U_CACHE = {}
+
+
+# Model.raydist_fn -> the curve id of include/ucnerf_march.h (UCN_RAYDIST_*).  coord.py:151-172 selects a callable by its
+# __name__ and inverts it through `inv_mapping`; the gin-bound callables are configs.py:13-19's torch functions.
+RAYDIST_CURVES = {None: 0, 'piecewise': 1, 'power_transformation': 2}
+RAYDIST_TORCH = {'reciprocal': 3, 'log': 4, 'exp': 5, 'sqrt': 6, 'square': 7}
+
+
+def raydist_curve(fn):
+    """The curve id of a Model.raydist_fn value, or ValueError for one the reference cannot invert (torch.log1p: missing from
+    inv_mapping, coord.py:164-172, a KeyError in its forward) or that is not one of the reference's curves."""
+    if fn is None or isinstance(fn, str):
+        if fn in RAYDIST_CURVES:
+            return RAYDIST_CURVES[fn]
+        raise ValueError(f"Model.raydist_fn={fn!r}: expected None, 'piecewise', 'power_transformation' or one of "
+                         f"torch.{', torch.'.join(RAYDIST_TORCH)}")
+    # gin hands over its configurable wrapper of the torch function (functools.wraps: same __name__, the function itself under
+    # __wrapped__), so the reference's selection by __name__ (coord.py:164-172) sees through it; the chain must end at the torch
+    # function of that name, because the kernels evaluate the curve themselves rather than call `fn`
+    name = getattr(fn, '__name__', None)
+    base = fn
+    while hasattr(base, '__wrapped__'):
+        base = base.__wrapped__
+    if name in RAYDIST_TORCH and base is getattr(torch, name):
+        return RAYDIST_TORCH[name]
+    if base is getattr(torch, str(name), None):
+        raise ValueError(f"Model.raydist_fn=torch.{name}: the reference has no inverse for it (coord.py:164-172 inv_mapping "
+                         f"holds {', '.join(RAYDIST_TORCH)})")
+    raise ValueError(f"Model.raydist_fn={fn!r}: only the reference's curves are supported (None, 'piecewise', "
+                     f"'power_transformation', torch.{', torch.'.join(RAYDIST_TORCH)}); the HIP kernels evaluate each "
+                     "curve and its inverse themselves (csrc/raydist.h)")
+
+
+def s_to_t(model, sdist, near, far, stream):
+    """models.py:208 `tdist = s_to_t(sdist)` on the device (ucn_s_to_t) for a model with a warped ray-distance curve; None for
+    the identity curve, whose kernels derive t from sdist, near and far themselves (nothing extra is launched)."""
+    curve = model._raydist_curve
+    if not curve:
+        return None
+    N, S1 = sdist.shape
+    tdist = torch.empty(N, S1, device=sdist.device)
+    _lib.check(_lib.load().ucn_s_to_t(sdist.data_ptr(), near.data_ptr(), far.data_ptr(), N, S1, curve,
+                                      float(model.power_lambda), tdist.data_ptr(), stream))
+    return tdist
 
 
 def _u_table(num_samples, train, device):
@@ -474,8 +519,9 @@ class Model(nn.Module):
         super().__init__()
         set_kwargs(self, kwargs)
         self.config = config
-        for k, want in dict(raydist_fn=None, learned_exposure_scaling=False,
-                            near_anneal_rate=None, single_mlp=False, distinct_prop=True, use_viewdirs=True).items():
+        self._raydist_curve = raydist_curve(self.raydist_fn)         # resolved once (coord.py:151-172); 0 = identity
+        for k, want in dict(learned_exposure_scaling=False, near_anneal_rate=None, single_mlp=False, distinct_prop=True,
+                            use_viewdirs=True).items():
             if getattr(self, k) != want:
                 raise NotImplementedError(f"Model.{k}={getattr(self, k)!r} is outside the shipped waymo.gin path")
         if self.bg_intensity_range[0] != self.bg_intensity_range[1]:
@@ -674,6 +720,12 @@ class Model(nn.Module):
                                         0 if jitter is None else jitter.shape[1], max_jitter, N, S,
                                         sdist.data_ptr(), st))
             _lib.check(lib.ucn_cone_basis(cam.data_ptr(), rvec.data_ptr(), N, basis.data_ptr(), st))
+            # a warped raydist_fn: the level's metric fenceposts once (models.py:208), read by the tdist siblings below
+            tdist = s_to_t(self, sdist, near, far, st)
+            march_features = lib.ucn_march_features if tdist is None else lib.ucn_march_features_tdist
+            composite = lib.ucn_composite if tdist is None else lib.ucn_composite_tdist
+            fence = (sdist, near, far) if tdist is None else (tdist,)          # geometry: what the kernels derive t from
+            fence_c = (sdist, near, far) if tdist is None else (tdist, far)    # compositing: + the batch's metric far
             prof = getattr(self, '_prof', None)
             prof_every = max(1, int(getattr(self, '_prof_every', 1)))
             # Two HIP streams: featurisation of pass i+1 (L2-request / VALU bound) runs beside the MLP of pass i
@@ -704,8 +756,8 @@ class Model(nn.Module):
                     side.wait_event(mlp_done[i_pass % 2])             # the buffer's previous reader
                 if timed:
                     e0.record(fstream)
-                _lib.check(lib.ucn_march_features(
-                    ctypes.byref(desc if mixed is None else mixed['desc']), sdist[sl].data_ptr(), near[sl].data_ptr(), far[sl].data_ptr(),
+                _lib.check(march_features(
+                    ctypes.byref(desc if mixed is None else mixed['desc']), *[t[sl].data_ptr() for t in fence],
                     o[sl].data_ptr(), d[sl].data_ptr(), basis[sl].data_ptr(), rad[sl].data_ptr(),
                     None if flip is None else flip[sl].data_ptr(), None if spin is None else spin[sl].data_ptr(),
                     float(self.std_scale), n, S, int(self.levels_per_block),
@@ -736,10 +788,10 @@ class Model(nn.Module):
                     rf = int(bool(self.rays_fastest))
                     _lib.check(lib.ucn_field_mlp(ctypes.byref(desc), fb.data_ptr(), n * S, S, rf, None, density[sl].data_ptr(),
                                                  None, None, st))
-                    _lib.check(lib.ucn_composite(density[sl].data_ptr(), None, sdist[sl].data_ptr(), near[sl].data_ptr(),
-                                                 far[sl].data_ptr(), d[sl].data_ptr(), float(self.bg_intensity_range[0]),
-                                                 int(bool(self.opaque_background)), n, S, weights[sl].data_ptr(), main[sl].data_ptr(),
-                                                 None, st))
+                    _lib.check(composite(density[sl].data_ptr(), None, *[t[sl].data_ptr() for t in fence_c],
+                                         d[sl].data_ptr(), float(self.bg_intensity_range[0]),
+                                         int(bool(self.opaque_background)), n, S, weights[sl].data_ptr(), main[sl].data_ptr(),
+                                         None, st))
                     if getattr(self, '_alive_idx', None) is None or self._alive_idx.numel() < n * S or self._alive_idx.device != dev:
                         self._alive_idx = torch.empty(max(n, nc) * S, dtype=torch.int32, device=dev)
                         self._alive_cnt = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -765,10 +817,10 @@ class Model(nn.Module):
                     prof.append((i_level, n, e0, e1, m0, e2))      # features: e0..e1 on its stream, MLP: m0..e2
             if overlap:
                 cur.wait_stream(side)
-            _lib.check(lib.ucn_composite(density.data_ptr(), _lib.ptr(rgbs), sdist.data_ptr(), near.data_ptr(),
-                                         far.data_ptr(), d.data_ptr(), float(self.bg_intensity_range[0]),
-                                         int(bool(self.opaque_background)), N, S, weights.data_ptr(),
-                                         main.data_ptr(), _lib.ptr(extras), st))
+            _lib.check(composite(density.data_ptr(), _lib.ptr(rgbs), *[t.data_ptr() for t in fence_c],
+                                 d.data_ptr(), float(self.bg_intensity_range[0]),
+                                 int(bool(self.opaque_background)), N, S, weights.data_ptr(),
+                                 main.data_ptr(), _lib.ptr(extras), st))
             rendering = dict(rgb=main[:, 0:3].reshape(prefix + (3,)), depth=main[:, 3].reshape(prefix),
                              acc=main[:, 4].reshape(prefix))
             if compute_extras:

@@ -38,7 +38,8 @@ class _GradChannel:
 
 
 class _FieldFeatures(torch.autograd.Function):
-    """features[N*S, L*C] = HIP featurisation of one level; backward scatters into the table gradient."""
+    """features[N*S, L*C] = HIP featurisation of one level; backward scatters into the table gradient.  `geom` = (sdist, near, far,
+    origins, directions, basis, radii, flip, spin), or with a warped Model.raydist_fn (tdist, origins, ...): the `_tdist` entry points."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
@@ -60,7 +61,8 @@ class _FieldFeatures(torch.autograd.Function):
         feat = torch.empty(N * S, L * C, device=embeddings.device)
         coord = torch.empty(N, S, 3, device=embeddings.device)
         tmean = torch.empty(N, S, device=embeddings.device)
-        _lib.check(lib.ucn_march_features(ctypes.byref(desc), *[_lib.ptr(t) for t in geom], float(std_scale), N, S,
+        march_features = lib.ucn_march_features if len(geom) == 9 else lib.ucn_march_features_tdist
+        _lib.check(march_features(ctypes.byref(desc), *[_lib.ptr(t) for t in geom], float(std_scale), N, S,
                                           int(lpb), layout, feat.data_ptr(), coord.data_ptr(), tmean.data_ptr(), _lib.stream()))
         ctx.mlp, ctx.geom, ctx.dims = mlp, geom, (N, S, float(std_scale), int(lpb))
         # the autocast step (half tables): the table gradient's row blocks accumulate in guaranteed-range fixed point (order-
@@ -104,7 +106,8 @@ class _FieldFeatures(torch.autograd.Function):
             else:
                 g, layout = g.contiguous(), 1
         ws = torch.empty(lib.ucn_march_features_backward_ws_floats(ctypes.byref(mlp.grid_field()), N, S), device=g.device)
-        _lib.check(lib.ucn_march_features_backward(ctypes.byref(mlp.grid_field()), *[_lib.ptr(t) for t in ctx.geom], std_scale,
+        backward = lib.ucn_march_features_backward if len(ctx.geom) == 9 else lib.ucn_march_features_backward_tdist
+        _lib.check(backward(ctypes.byref(mlp.grid_field()), *[_lib.ptr(t) for t in ctx.geom], std_scale,
                                                    N, S, 0, layout | (_lib.BWD_FIXED_POINT if ctx.fixed else 0), g.data_ptr(), grad.data_ptr(),
                                                    ws.data_ptr(), _lib.stream()))
         return grad, None, None, None, None, None, None, None, None
@@ -995,20 +998,20 @@ def _zeros_ro(n, k, device):
 
 class _Composite(torch.autograd.Function):
     """render.py:155-174 + :203-216 as the rendering kernel `ucn_composite` (forward) and `ucn_composite_backward`:
-    weights, rgb, depth, acc of N rays from density [N,S] and rgbs [N,S,3]; sample positions carry no gradient."""
+    weights, rgb, depth, acc of N rays from density [N,S] and rgbs [N,S,3]; sample positions carry no gradient.
+    tdist (a warped Model.raydist_fn): the metric fenceposts, read by the `_tdist` entry points instead of sdist / near."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
-    def forward(ctx, density, rgbs, sdist, near, far, dirs, bg, opaque):
+    def forward(ctx, density, rgbs, sdist, near, far, dirs, bg, opaque, tdist=None):
         lib = _lib.load()
         N, S = density.shape
         density, rgbs = density.contiguous(), rgbs.contiguous()
         weights = torch.empty(N, S, device=density.device)
         main = torch.empty(N, 5, device=density.device)
-        _lib.check(lib.ucn_composite(density.data_ptr(), rgbs.data_ptr(), sdist.data_ptr(), near.data_ptr(), far.data_ptr(),
-                                     dirs.data_ptr(), float(bg), int(bool(opaque)), N, S, weights.data_ptr(), main.data_ptr(),
-                                     None, _lib.stream()))
-        ctx.save_for_backward(density, rgbs, sdist, near, far, dirs)
+        _lib.check(_composite_call(lib, density, rgbs, sdist, near, far, tdist, dirs, float(bg), int(bool(opaque)), N, S, weights,
+                                   main, None))
+        ctx.save_for_backward(density, rgbs, sdist, near, far, dirs, tdist)
         ctx.consts = (float(bg), int(bool(opaque)))
         # outputs nobody differentiates (depth and acc always, rgb at a proposal level) arrive as None in backward instead of as
         # zero tensors autograd fills first: 12 launches per step less (tools/train_launch_sites.py)
@@ -1019,10 +1022,10 @@ class _Composite(torch.autograd.Function):
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, g_w, g_rgb, g_depth, g_acc):
         lib = _lib.load()
-        density, rgbs, sdist, near, far, dirs = ctx.saved_tensors
+        density, rgbs, sdist, near, far, dirs, tdist = ctx.saved_tensors
         N, S = density.shape
         if g_w is None and g_rgb is None and g_depth is None and g_acc is None:
-            return None, None, None, None, None, None, None, None
+            return None, None, None, None, None, None, None, None, None
         if g_depth is None and g_acc is None:
             # the usual case: one cat against a cached block of zeros (read-only) instead of a fill and up to three strided copies
             g_main = _zeros_ro(N, 5, density.device) if g_rgb is None else torch.cat([g_rgb.float(), _zeros_ro(N, 2, density.device)], dim=1)
@@ -1037,10 +1040,25 @@ class _Composite(torch.autograd.Function):
         g_w = None if g_w is None else g_w.float().contiguous()
         g_density = torch.empty_like(density)
         g_rgbs = torch.empty_like(rgbs)
-        _lib.check(lib.ucn_composite_backward(density.data_ptr(), rgbs.data_ptr(), sdist.data_ptr(), near.data_ptr(),
-                                              far.data_ptr(), dirs.data_ptr(), *ctx.consts, N, S, _lib.ptr(g_w),
-                                              g_main.data_ptr(), g_density.data_ptr(), g_rgbs.data_ptr(), _lib.stream()))
-        return g_density, g_rgbs, None, None, None, None, None, None
+        if tdist is None:
+            _lib.check(lib.ucn_composite_backward(density.data_ptr(), rgbs.data_ptr(), sdist.data_ptr(), near.data_ptr(),
+                                                  far.data_ptr(), dirs.data_ptr(), *ctx.consts, N, S, _lib.ptr(g_w),
+                                                  g_main.data_ptr(), g_density.data_ptr(), g_rgbs.data_ptr(), _lib.stream()))
+        else:
+            _lib.check(lib.ucn_composite_backward_tdist(density.data_ptr(), rgbs.data_ptr(), tdist.data_ptr(), dirs.data_ptr(),
+                                                        *ctx.consts, N, S, _lib.ptr(g_w), g_main.data_ptr(), g_density.data_ptr(),
+                                                        g_rgbs.data_ptr(), _lib.stream()))
+        return g_density, g_rgbs, None, None, None, None, None, None, None
+
+
+def _composite_call(lib, density, rgbs, sdist, near, far, tdist, dirs, bg, opaque, N, S, weights, main, extras):
+    """ucn_composite, or ucn_composite_tdist on the metric fenceposts of a warped curve (far stays the batch's metric far)."""
+    if tdist is None:
+        return lib.ucn_composite(density.data_ptr(), rgbs.data_ptr(), sdist.data_ptr(), near.data_ptr(), far.data_ptr(),
+                                 dirs.data_ptr(), bg, opaque, N, S, weights.data_ptr(), main.data_ptr(), _lib.ptr(extras),
+                                 _lib.stream())
+    return lib.ucn_composite_tdist(density.data_ptr(), rgbs.data_ptr(), tdist.data_ptr(), far.data_ptr(), dirs.data_ptr(), bg,
+                                   opaque, N, S, weights.data_ptr(), main.data_ptr(), _lib.ptr(extras), _lib.stream())
 
 
 class _HashDecay(torch.autograd.Function):
@@ -1425,7 +1443,7 @@ def brightness_forward(bc, idx, which="latent_code"):
 def march_train(model, rand, batch, train_frac, compute_extras, eval_camidx, glo_vec=None):
     """Model.forward with an autograd graph (ref models.py:97-365).  glo_vec [N, num_glo_features] (or None): the NeRF level's
     per-ray GLO codes (models.py:118-127); the proposal levels get none (models.py:226)."""
-    from .models import _f32, _u_table
+    from .models import _f32, _u_table, s_to_t
     lib = _lib.load()
     model.last_march_route = 'train_graph'
     origins = batch['origins']
@@ -1494,7 +1512,8 @@ def march_train(model, rand, batch, train_frac, compute_extras, eval_camidx, glo
             # either (stepfun.py:251-294 works on detached weights).
             sdist = _f32(pn_s, N, S + 1).clone()
         _lib.check(lib.ucn_cone_basis(cam.data_ptr(), rvec.data_ptr(), N, basis.data_ptr(), st))
-        geom = (sdist, near, far, o, d, basis, rad, flip, spin)
+        tdist = s_to_t(model, sdist, near, far, st)              # a warped raydist_fn: metric fenceposts (models.py:208), else None
+        geom = ((sdist, near, far) if tdist is None else (tdist,)) + (o, d, basis, rad, flip, spin)
         half_table = torch.is_autocast_enabled() and mlp.encoder.level_dim % 2 == 0 and getattr(model, 'autocast_half_tables', True)
         chan = _GradChannel()                        # `feat` has exactly one consumer, the heads below: the two nodes may agree on its gradient's layout
         feat, coord, tmean = _FieldFeatures.apply(mlp.encoder.embeddings, mlp, geom, N, S, model.std_scale,
@@ -1504,7 +1523,7 @@ def march_train(model, rand, batch, train_frac, compute_extras, eval_camidx, glo
         if getattr(cfg, 'brightness_correction', False):              # models.py:233-235 (gated on this flag)
             rgbs, density = GradientScaler.apply(rgbs, density, tmean)
         weights, c_rgb, c_depth, c_acc = _Composite.apply(density, rgbs, sdist, near, far, d,
-                                                          float(model.bg_intensity_range[0]), model.opaque_background)
+                                                          float(model.bg_intensity_range[0]), model.opaque_background, tdist)
         rendering = dict(rgb=c_rgb, depth=c_depth, acc=c_acc)
         rendering = {k: v.reshape(prefix + v.shape[1:]) for k, v in rendering.items()}
         rendering['weights'] = weights.reshape(prefix + (S,))
@@ -1514,9 +1533,8 @@ def march_train(model, rand, batch, train_frac, compute_extras, eval_camidx, glo
             with torch.no_grad():
                 dn, rg = density.detach().float().contiguous(), rgbs.detach().float().contiguous()
                 w_x, main_x, extras = torch.empty(N, S, device=dev), torch.empty(N, 5, device=dev), torch.empty(N, 4, device=dev)
-                _lib.check(lib.ucn_composite(dn.data_ptr(), rg.data_ptr(), sdist.data_ptr(), near.data_ptr(), far.data_ptr(),
-                                             d.data_ptr(), float(model.bg_intensity_range[0]), int(bool(model.opaque_background)),
-                                             N, S, w_x.data_ptr(), main_x.data_ptr(), extras.data_ptr(), st))
+                _lib.check(_composite_call(lib, dn, rg, sdist, near, far, tdist, d, float(model.bg_intensity_range[0]),
+                                           int(bool(model.opaque_background)), N, S, w_x, main_x, extras))
             rendering['distance_mean'] = extras[:, 0].reshape(prefix)
             rendering['distance_percentile_5'] = extras[:, 1].reshape(prefix)
             rendering['distance_median'] = extras[:, 2].reshape(prefix)
