@@ -96,3 +96,24 @@ def pin_noise(batch, noise, device="cuda"):
         b["march_noise"] = [dict(jitter=nz.jitter.to(device), flip=nz.flip.to(device), spin=nz.spin.to(device))
                             for nz in noise]
     return b
+
+
+# ------------------------------------------------------------------ bracket: fp32 reference and HIP against the float64 truth
+def bracket(name, e_ref, e_hip, k=2.0, floor=(1e-6, 1e-7), min_ref=None):
+    """e_ref = |fp32 oracle - float64 truth|, e_hip = |HIP - truth| on identical inputs (oracle/truth64.py).  Prints one report
+    line, then asserts (1) with `min_ref`: the reference itself is at least that far from the truth somewhere (otherwise the
+    bracket says nothing), (2) e_hip.max() <= k e_ref.max() + floor[0] and e_hip.mean() <= k e_ref.mean() + floor[1].
+    Returns (ratio of the maxima, ratio of the means)."""
+    e_ref = torch.as_tensor(e_ref).double().reshape(-1)
+    e_hip = torch.as_tensor(e_hip).double().reshape(-1)
+    assert e_ref.shape == e_hip.shape and e_ref.numel() > 0, (name, e_ref.shape, e_hip.shape)
+    assert bool(torch.isfinite(e_ref).all()) and bool(torch.isfinite(e_hip).all()), name
+    rm_, ra, hm, ha = float(e_ref.max()), float(e_ref.mean()), float(e_hip.max()), float(e_hip.mean())
+    r_max, r_mean = hm / max(rm_, 1e-300), ha / max(ra, 1e-300)
+    print(f"BRACKET {name}: e_ref max {rm_:.3e} mean {ra:.3e} | e_hip max {hm:.3e} mean {ha:.3e} | "
+          f"ratio max {r_max:.3f} mean {r_mean:.3f} | k {k:g}")
+    if min_ref is not None:
+        assert rm_ >= min_ref, (name, "the float32 reference is not measurably off the truth here", rm_, min_ref)
+    assert hm <= k * rm_ + floor[0], (name, "max", hm, rm_, k)
+    assert ha <= k * ra + floor[1], (name, "mean", ha, ra, k)
+    return r_max, r_mean

@@ -372,6 +372,7 @@ def test_field_vs_golden():
     # differ by an ulp between libraries) moves a level-15 (res 524288) lookup by ~0.03 cell, i.e.
     # O(1e-2) in that level's feature before erf damping.  The 6-level PropMLP grid (res <= 512) has
     # no such amplification and is held to 1e-6.  See DESIGN.md "Parity analysis".
+    # (bracketed by the reference's own float64 error in test_bracket_gpu.py::test_field_golden_bracket: 2.2e-4 / 1.0e-4 / 1.9e-3)
     tol = dict(nerf=dict(density=1e-3, rgb=3e-4), prop=dict(density=1e-6, rgb=0.0))
     for name, mlp in (("nerf", model.nerf_mlp), ("prop", model.prop_mlp_0)):
         res = mlp(False, means, stds, viewdirs=vd)
@@ -421,6 +422,8 @@ def test_model_forward_vs_golden(name, kind, over):
         r = rend[lvl]
         last = lvl == spec.num_levels - 1
         samp = (1e-2 if fine else 2e-4) if last else 2e-6          # per-sample density / colour
+        # (1e-2 is 1-2 decades looser than 2 x the float32 reference's own float64 error on these specs:
+        # test_bracket_gpu.py::test_fine_level_features_density_colour_bracket holds that, per level and per sample)
         assert H.maxdiff(hist[lvl]["sdist"].cpu(), g("hist_sdist").reshape(hist[lvl]["sdist"].shape)) <= (5e-5 if last else 0.0), lvl
         assert H.maxdiff(hist[lvl]["density"].cpu().reshape(-1), g("hist_density").reshape(-1)) <= samp, lvl
         assert H.maxdiff(r["weights"].cpu().reshape(-1), g("weights").reshape(-1)) <= (2e-4 if last else 5e-7), lvl
@@ -1118,6 +1121,7 @@ def test_cone_cast_and_contraction_vs_reference_golden():
         got = _cast_probe(fx, fx[f"{tag}_rand_vec"], **kw)
         means, stds, t = fx[f"{tag}_means"], fx[f"{tag}_stds"], fx[f"{tag}_t"]
         # every one of the 6 multisamples separately: a swapped / mirrored hexagon offset that keeps the mean of six fails here.
+        # (test_bracket_gpu.py::test_cone_cast_and_contraction_bracket holds the same outputs to 2 x the float32 oracle's float64 error)
         # |means| up to ~8: 2 ulp of 8 = 2e-6 (the eval pattern's cos / sin are host constants, the train draws go through
         # v_sin / v_cos with ~1e-6 absolute error on an offset of size r t / sqrt(2) ~ 1e-3 t)
         assert H.maxdiff(got[..., 0:3], means) <= 4e-6, tag
@@ -1239,51 +1243,12 @@ def test_the_frame_exchange_runs_on_rccl(tmp_path, inplace):
 # semantics (the oracle = the golden's values) has its own distance to it, and the HIP path must be within a small factor
 # of THAT distance -- per sample, not per pixel.
 def _truth_density64(fs, sd, means, stds):
-    """models.py:485-512 in float64: contraction (coord.py:60-72), / 2, the hash-grid interpolation of gridencoder.cu:87-199
-    (level scale and resolution are the reference's float32 constants, cell indices exact integers, fractional weights and
-    sums in float64), erf damping with the reference's int32-wrapped grid_sizes**2 (models.py:495), mean of 6, density MLP."""
-    import numpy as np
-    from oracle import grid_numpy as gn
-    pls, offsets, grid_sizes, _ = fs.layout()
-    m = means.double().reshape(-1, 3)
-    s = stds.double().reshape(-1)
-    n2 = (m ** 2).sum(-1, keepdim=True).clamp_min(float(rm.EPS))
-    root = n2.sqrt()
-    inside = n2 <= 1
-    z = torch.where(inside, m, ((2 * root - 1) / n2) * m) / 2
-    sc = torch.where(inside[:, 0], s, ((2 * root[:, 0] - 1) ** (1 / 3) / root[:, 0]) ** 2 * s) / 2
-    x = ((z + 1) / 2).numpy()
-    table = sd[fs.prefix + ".encoder.embeddings"].double().numpy()
-    off = np.asarray(offsets)
-    scale, res, rows = gn.level_geometry(off, float(np.log2(pls)), fs.grid_base_resolution)     # layout() hands back the per-level scale itself
-    L, C = len(scale), table.shape[1]
-    feats = np.zeros((x.shape[0], L, C))
-    oob = ((x < 0) | (x > 1)).any(axis=1)
-    with np.errstate(over="ignore"):
-        for l in range(L):
-            p = x * float(scale[l]) + 0.5
-            cell = np.floor(p).astype(np.uint32)
-            f = p - np.floor(p)
-            tab = table[off[l]:off[l + 1]]
-            acc = np.zeros((x.shape[0], C))
-            for k in range(8):
-                w = np.ones(x.shape[0])
-                corner = cell.copy()
-                for dd in range(3):
-                    if k & (1 << dd):
-                        w = w * f[:, dd]
-                        corner[:, dd] += np.uint32(1)
-                    else:
-                        w = w * (1 - f[:, dd])
-                acc += w[:, None] * tab[gn.rows_of(corner, rows[l], res[l])]
-            acc[oob] = 0
-            feats[:, l] = acc
-    gs2 = (torch.as_tensor(grid_sizes).to(torch.int32) ** 2).double()            # the reference's int32 wrap
-    damp = torch.erf(1 / torch.sqrt(8 * sc[:, None] ** 2 * gs2[None, :]))
-    feat = (torch.from_numpy(feats) * damp[..., None]).reshape(means.shape[:-1] + (L, C)).mean(dim=-3).flatten(-2, -1)
-    W = lambda k: sd[fs.prefix + "." + k].double()
-    h = torch.relu(feat @ W("density_layer.0.weight").T + W("density_layer.0.bias"))
-    return (h @ W("density_layer.2.weight").T + W("density_layer.2.bias"))[..., 0], feat
+    """models.py:485-512 in float64 (oracle/truth64.py: contraction, / 2, hash-grid interpolation with the reference's float32
+    level constants and exact integer cells, erf damping with the int32-wrapped grid_sizes ** 2, mean of 6, density MLP)."""
+    from oracle import truth64 as t64
+    with torch.no_grad():
+        res = t64.field_forward(fs, t64.state64(sd), means, stds)
+    return res["raw_density"], res["features"].flatten(-2, -1)
 
 
 def test_fine_level_per_sample_error_is_bracketed_by_the_float32_reference_itself():

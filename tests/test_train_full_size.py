@@ -152,6 +152,10 @@ def _table_bar(name, lvl):
     # levels a row sees a handful of samples and the gradient reaching it went through the 16-level featurisation's
     # noise floor (DESIGN.md "Parity analysis": 1e-7 differences in a sample position, amplified by resolutions up to
     # 2^19), so single rows move by percents while the level's sums hold.
+    # (the featurisation's own table gradient is bracketed per level by the float32 oracle's float64 error in
+    # test_bracket_gpu.py::test_table_gradient_bracket_full_size: 1e-6 at side 17 (four decades below this bar) ... 3e-2 at side
+    # 524 289; through the whole step the float32 oracle itself is 0.3 - 3.5 % off a float64 evaluation on every level, and HIP
+    # is held to 2 x that in test_training_step_table_gradient_bracket_config_B)
     return 3e-2 if lvl < 4 else 1e-1        # measured 0.4 - 1.4 % / 1.4 - 3.4 % (profiles/r05/full_train_test_vs_oracle.txt)
 
 

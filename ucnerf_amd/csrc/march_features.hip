@@ -23,9 +23,14 @@
 //     (y+1)*P == y*P + P);
 //   * quantities that only feed the erf damping (std) use fast reciprocals / exp2-log2 instead of
 //     IEEE division and powf, and erf itself is the Abramowitz-Stegun 7.1.26 form (|err| <= 1.5e-7);
-//     everything that feeds a COORDINATE keeps the reference's exact fp32 op sequence
-//     (correctly-rounded div/sqrt, no contraction), so positions -- and the interpolated features
-//     for given positions -- stay bit-identical to the oracle.
+//     everything that feeds a COORDINATE uses correctly-rounded div/sqrt and no contraction.  Measured
+//     (tests/test_bracket_gpu.py, profiles/bracket/bracket_report.txt): 3806 of 3828 eval-pattern and
+//     3785 of 3828 training-pattern multisample positions of the cast fixture are bit-identical to the
+//     reference's, the others differ by <= 4.8e-7 (1 ulp of 8: the 3-term basis sum is associated
+//     differently, the training angles go through v_sin / v_cos); against a float64 evaluation the
+//     kernel's positions are as far off as the reference's own float32 ones (ratio 0.87 - 1.00).  The
+//     interpolation for GIVEN float32 positions is bit-identical to the reference's (fixed fmaf chain);
+//     the fast-math contracted std is up to 2.4x the reference's own float32 error (9e-7 relative).
 #include "ucn_common.h"
 #include "wave_dpp.h"
 #include "raydist.h"
