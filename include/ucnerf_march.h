@@ -255,7 +255,11 @@ int ucn_points_features(const ucn_field_t *f, const float *means, const float *s
 /* ref: coord.py:214-225 pos_enc(viewdirs): the per-ray direction inputs of the colour MLP.
  * mlp_mode 0: folded through the direction columns of lin_second_stage_{0,1} into additive terms
  *             [N,2,n_width];  mlp_mode 1: the encoding itself as one 32-wide input tile [N,32]
- *             (k < n_dir: pos_enc, k = n_dir: 1 -- the bias slot, then 0).
+ *             (k < n_dir: pos_enc, k = n_dir: 1 -- the bias slot, then 0).  ABI 27: a 256-wide field's row is
+ *             [N, 32 + 2*n_width]: behind the tile, the ray's additive terms of the two COMPOSED colour layers
+ *             (direction columns and bias column of ucn_field_pack's matrices, times the layer's power-of-two
+ *             scale, in accumulator-slot order) -- so in mode 1 f->packed must have been packed, and the
+ *             buffer is refreshed after every ucn_field_pack.  Row stride = ucn_field_dir_floats(f, 1).
  * ucn_field_dir_floats = number of floats of dir_bias_out for N rays in the field's mode. */
 uint64_t ucn_field_dir_floats(const ucn_field_t *f, uint32_t N);
 int ucn_field_dir_bias(const ucn_field_t *f, const float *viewdirs /*[N,3]*/, uint32_t N,

@@ -190,7 +190,7 @@ extern "C" uint64_t ucn_field_packed_floats(const ucn_field_t *f) {
 extern "C" uint64_t ucn_field_dir_floats(const ucn_field_t *f, uint32_t N) {
     PackPlan pl;
     if (make_plan(f, &pl) || pl.prop) return 0;
-    return f->mlp_mode == 1 ? (uint64_t)N * 32 : (uint64_t)N * 2 * f->n_width;
+    return f->mlp_mode == 1 ? (uint64_t)N * dir_stride_h(f->n_width) : (uint64_t)N * 2 * f->n_width;
 }
 
 extern "C" int ucn_field_pack(const ucn_field_t *f, ucn_stream_t stream) {
@@ -235,7 +235,7 @@ extern "C" int ucn_field_dir_bias(const ucn_field_t *f, const float *viewdirs, u
     UCN_REQUIRE((f->n_dir - 3) % 6 == 0, "field_dir_bias: n_dir must be 3+6*deg, got %u", f->n_dir);
     if (N == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    if (f->mlp_mode == 1) return ucn_h_dir_enc(f, viewdirs, N, dir_bias_out, st);
+    if (f->mlp_mode == 1) return ucn_h_dir_enc(f, pl, viewdirs, N, dir_bias_out, st);
     const dim3 grid(ucn_div_up(N, 16));
     if (f->n_width == 256)
         hipLaunchKernelGGL(k_dir_bias<256>, grid, dim3(256), 0, st, viewdirs, f->w_c0, f->w_c1, f->n_bottleneck, f->n_dir, N, dir_bias_out);
@@ -270,6 +270,7 @@ extern "C" int ucn_field_mlp(const ucn_field_t *f, const float *features, uint32
     a.n_rays = B / samples_per_ray; a.rays_fastest = (rays_fastest & 1) ? 1u : 0u;
     a.small_ring = (rays_fastest & UCN_LAUNCH_CORESIDENT) ? 1u : 0u;
     a.idx = g_mlp_idx; a.count = g_mlp_count;
+    a.dstride = dir_stride_h(f->n_width); a.prt = 0;
     a.n_chunks = pl.n_groups / kChunkGroups;
     a.p0 = pl.p0; a.pstream = pl.pstream; a.phead = pl.phead;
     a.density_bias = f->density_bias; a.rgb_premult = f->rgb_premultiplier; a.rgb_bias = f->rgb_bias;

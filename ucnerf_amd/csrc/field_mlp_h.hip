@@ -32,6 +32,16 @@
 //    (|features| ~ 1e-4) or a trained one with large pre-activations both keep fp32-class products
 //    (tests/test_gpu_parity.py::test_split_f16_range).
 //
+// 6. RAY TILES (k_field_mlp_h8<..., MODE = 1>: the rendering default of the 256-wide field).  The direction tile of comment 3 depends
+//    on the ray only, so its contribution to each composed layer is ONE NW-vector per ray: M_A[:, dir] d + M_A[:, bias] and the same
+//    with M_B.  When the 32 columns of a wave's tile are 32 consecutive samples of ONE ray, that vector is the same for every column:
+//    in the 32x32 accumulator layout 16 floats per lane and output tile, a function of (row, h) only.  k_dir_terms writes it once per
+//    ray (fp32 FMAs, on the accumulators' power-of-two scale, in accumulator-slot order) behind the ray's direction tile; each wave
+//    brings its ray's 2 KiB into LDS beside the side table (LDS-DMA, in front of the ring), and the accumulators of every output pair
+//    start from those values instead of zero.  The third input tile disappears from the stream (its own, 400 instead of 464 KiB),
+//    from the MFMAs (600 instead of 696 per tile), from the operand reads and from the registers.  A workgroup's four waves are four
+//    NEIGHBOURING rays at the same 32 samples: in the gather's rays-fastest feature buffer they share every line they touch.
+//
 // Packed layout (floats at ucn_field_t::packed + pstream; 1 KiB = 256-float groups):
 //   side table, kSideGroups groups:
 //       [0,64)     b_d0 2^e_h0 as two bias tiles [tile][h][16]
@@ -42,6 +52,7 @@
 //       A   composed layer 0         [otp][it < 3][s][o2]                       M_A = [W_c0x W_d1 | W_c0 dir | bias | 0]
 //       B   for each output pair otp: skip part [it < 3][s][o2] of M_B = [W_c1x W_d1 | W_c1 dir | bias | 0],
 //                                     then      [it < NTW][s][o2] of W_c1[:, 0:NW]
+//   ray-tile stream (256-wide fields; at group PackPlan::rt_group): the same with it < 2 in A and in B's skip part
 #include "field_plan.h"
 #include "wave_dpp.h"
 #include "mlp_ring.h"
@@ -71,6 +82,55 @@ __global__ __launch_bounds__(256) void k_dir_enc(const float *__restrict__ viewd
         v = k == ndir ? 1.0f : 0.0f;
     }
     out[i] = ldexpf(v, kDirExp);
+}
+
+// 256-wide fields: per ray the direction tile of k_dir_enc (floats [0, 32) of the ray's row) and behind it the ray's direction
+// terms of the two composed layers, on the accumulators' scale and in accumulator-slot order (comment 6 at the top):
+//   out[ray][32 + (l*8 + t)*32 + h*16 + r] = 2^e_l (sum_k M_l[n][64 + k] enc[k] + M_l[n][64 + ND]),  n = acc_row(t, r, h),
+// l = 0: M_A, e_h1;  l = 1: M_B, e_h2.  fp32 FMAs over <= 28 exact fp32 terms: no less exact than the split-f16 products they replace.
+__global__ __launch_bounds__(256) void k_dir_terms(const float *__restrict__ viewdirs, const float *__restrict__ MA,
+                                                   const float *__restrict__ MB, const int *__restrict__ exps, uint32_t ndir,
+                                                   uint32_t N, float *__restrict__ out) {
+    constexpr uint32_t RB = 32, STRIDE = 32 + 512;   // rays per workgroup; dir_stride_h(256)
+    __shared__ float enc[RB][32];
+    const uint32_t ray0 = blockIdx.x * RB;
+    const uint32_t deg = (ndir - 3u) / 6u;
+    for (uint32_t i = threadIdx.x; i < RB * 32u; i += 256u) {
+        const uint32_t rl = i >> 5, k = i & 31u;
+        const uint32_t ray = ray0 + rl < N ? ray0 + rl : N - 1;
+        float v;
+        if (k < 3u) {
+            v = viewdirs[ray * 3 + k];
+        } else if (k < ndir) {
+            const uint32_t kk = (k - 3u) % (3u * deg), a = kk % 3u, si = kk / 3u;
+            const float sc = viewdirs[ray * 3 + a] * (float)(1u << si);
+            v = (k - 3u) < 3u * deg ? sinf(sc) : sinf(sc + 1.5707963705062866f);
+        } else {
+            v = k == ndir ? 1.0f : 0.0f;
+        }
+        enc[rl][k] = v;
+        if (ray0 + rl < N) out[(size_t)(ray0 + rl) * STRIDE + k] = ldexpf(v, kDirExp);
+    }
+    __syncthreads();
+    const uint32_t t = threadIdx.x >> 5, h = (threadIdx.x >> 4) & 1u, r = threadIdx.x & 15u;
+    const uint32_t n = acc_row(t, r, h);
+    float wa[28], wb[28];                            // columns 64 .. 64 + ndir: the direction weights and the composed bias
+#pragma unroll
+    for (uint32_t k = 0; k < 28u; k++) {
+        wa[k] = k <= ndir ? ldexpf(MA[n * kCompCols + 64u + k], exps[E_H1]) : 0.0f;
+        wb[k] = k <= ndir ? ldexpf(MB[n * kCompCols + 64u + k], exps[E_H2]) : 0.0f;
+    }
+    for (uint32_t rl = 0; rl < RB && ray0 + rl < N; rl++) {
+        float sa = 0.0f, sb = 0.0f;
+#pragma unroll
+        for (uint32_t k = 0; k < 28u; k++) {         // enc[ndir] = 1: the bias column rides along; enc beyond = 0
+            sa = fmaf(wa[k], enc[rl][k], sa);
+            sb = fmaf(wb[k], enc[rl][k], sb);
+        }
+        float *o = out + (size_t)(ray0 + rl) * STRIDE + 32u + threadIdx.x;
+        o[0] = sa;
+        o[256] = sb;
+    }
 }
 
 // M[j][c], j < NW, c < kCompCols:  c < 64: sum_i Wout[j][col0+i] W_d1[i][c]  |  c-64 < ND: Wout[j][col0+NB+c-64]
@@ -317,7 +377,7 @@ __global__ __launch_bounds__(256) void k_field_mlp_h(MlpArgs a) {
     load_features<kKS>(a, b, h, fv);
     f32x16 ev;
     if constexpr (RGB) {
-        const float4 *ep = reinterpret_cast<const float4 *>(a.dir_bias + (size_t)ray_index(a, b) * 32 + 4 * h);
+        const float4 *ep = reinterpret_cast<const float4 *>(a.dir_bias + (size_t)ray_index(a, b) * a.dstride + 4 * h);
 #pragma unroll
         for (int r4 = 0; r4 < 4; r4++) {
             const float4 v = ep[2 * r4];
@@ -471,8 +531,21 @@ __global__ __launch_bounds__(256) void k_field_mlp_h(MlpArgs a) {
 // on the matrix pipe: one computes while the other splits / runs the rgb head / waits for LDS.  That needs <= 256
 // registers per lane: ONE accumulator pair, nothing in MFMA shadows (the partner wave is the shadow), a short
 // operand pipe.
-template <int NTW, int NWAVES, int CHUNK, int SLOTS, int LEAD, int DEPTH>
+//
+// Ray tiles (MODE 1; comment 6 at the top; NWAVES = 4, no compaction list, samples_per_ray % 32 == 0): a wave's tile is 32 consecutive samples of
+// one ray.  Rays-fastest features: workgroup = 4 neighbouring rays x the same 32 samples, workgroups ray-group-fastest; otherwise the
+// plain tile order (a [ray][sample] batch's tiles ARE ray tiles).  LDS: [side table, kSideUsed groups][4 x 2 KiB direction terms][ring].
+constexpr int kSideUsed = 5;                         // groups of the side table that hold anything (floats [0, 1280))
+constexpr int kRtLdsGroups = kSideUsed + 8;          // ray-tile kernel: the ring starts here
+//
+// MODE 0: the direction tile is the third input tile (comment 3).  MODE 1: ray tiles.  MODE 2: the [any rays][32] tile with the SAME
+// arithmetic per sample as MODE 1 -- the ray-tile stream, and every lane fetches its own ray's seeds from global memory, pair by pair
+// (compiler-visible loads in the middle of the LDS-DMA stream: each one costs the ring its look-ahead).  It serves the
+// launches whose samples must agree BIT FOR BIT with a ray-tile launch of the same rays: the compacted colour pass and the co-resident
+// shape (tests hold both to the plain launch with torch.equal).
+template <int NTW, int NWAVES, int CHUNK, int SLOTS, int LEAD, int DEPTH, int MODE>
 __global__ __launch_bounds__(NWAVES * 64, 2) void k_field_mlp_h8(MlpArgs a) {
+    constexpr bool RT = MODE == 1, SEEDED = MODE != 0;
 #ifdef UCN_EXP_TIMING
     const unsigned long long t_begin = __builtin_readcyclecounter();
 #define UCN_STAMP8(i) do { if (blockIdx.x == UCN_EXP_TIMING && (threadIdx.x & 255) == 0) a.bott[(threadIdx.x >> 8) * 32 + (i)] = (float)(__builtin_readcyclecounter() - t_begin); } while (0)
@@ -483,27 +556,50 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void k_field_mlp_h8(MlpArgs a) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int j = lane & 31, h = lane >> 5;
-    const uint32_t b0 = (blockIdx.x * NWAVES + wave) * 32u;
-    bool live = b0 + j < a.B;
-    uint32_t b = live ? b0 + j : a.B - 1;
-    if (a.idx) {                                         // compacted colour pass (see k_field_mlp_h)
-        const uint32_t cnt = *a.count;
-        if (blockIdx.x * (NWAVES * 32u) >= cnt) return;
-        live = b0 + j < cnt;
-        b = a.idx[live ? b0 + j : cnt - 1];
+    bool live;
+    uint32_t b, oi, ray = 0;
+    if constexpr (RT) {
+        static_assert(NWAVES == 4, "ray tiles: four neighbouring rays per workgroup");
+        const uint32_t tiles = a.spr >> 5;               // per ray
+        uint32_t s0;
+        if (a.rays_fastest) {
+            const uint32_t groups = (a.n_rays + 3u) >> 2, st = blockIdx.x / groups;
+            ray = (blockIdx.x - st * groups) * 4u + wave;
+            s0 = st * 32u;
+        } else {
+            const uint32_t t = blockIdx.x * 4u + wave;
+            ray = t / tiles;
+            s0 = (t - ray * tiles) * 32u;
+        }
+        live = ray < a.n_rays;                           // wave-uniform; a dead wave computes on the last ray and stores nothing
+        ray = live ? ray : a.n_rays - 1;
+        b = a.rays_fastest ? (s0 + j) * a.n_rays + ray : ray * a.spr + s0 + j;
+        oi = ray * a.spr + s0 + j;
+    } else {
+        const uint32_t b0 = (blockIdx.x * NWAVES + wave) * 32u;
+        live = b0 + j < a.B;
+        b = live ? b0 + j : a.B - 1;
+        if (a.idx) {                                     // compacted colour pass (see k_field_mlp_h)
+            const uint32_t cnt = *a.count;
+            if (blockIdx.x * (NWAVES * 32u) >= cnt) return;
+            live = b0 + j < cnt;
+            b = a.idx[live ? b0 + j : cnt - 1];
+        }
+        oi = out_index(a, b);
     }
-    const uint32_t oi = out_index(a, b);
     constexpr int NP = NTW / 2;
+    constexpr int NI = SEEDED ? 2 : 3;                       // input tiles of the composed layers: h0, and the direction tile
     constexpr int GA = 4 * kKS;
-    constexpr int GB = GA + NP * 24;
-    constexpr int PB = 24 + NTW * 8;
+    constexpr int GB = GA + NP * NI * 8;
+    constexpr int PB = NI * 8 + NTW * 8;
     constexpr int NG = GB + NP * PB;
+    constexpr int SIDE = RT ? kSideUsed : kSideGroups, RING0 = RT ? kRtLdsGroups : kSideGroups;
 
     float fv[kKS][8];
     load_features<kKS>(a, b, h, fv);
     f32x16 ev;
-    {
-        const float4 *ep = reinterpret_cast<const float4 *>(a.dir_bias + (size_t)ray_index(a, b) * 32 + 4 * h);
+    if constexpr (!SEEDED) {
+        const float4 *ep = reinterpret_cast<const float4 *>(a.dir_bias + (size_t)ray_index(a, b) * a.dstride + 4 * h);
 #pragma unroll
         for (int r4 = 0; r4 < 4; r4++) {
             const float4 v = ep[2 * r4];
@@ -511,13 +607,36 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void k_field_mlp_h8(MlpArgs a) {
         }
     }
     const float *side = s_lds;
-    Ring<NG, CHUNK, NWAVES, SLOTS, LEAD> ring(a.packed + a.pstream + kSideGroups * 256, s_lds + kSideGroups * 256, lane, wave);
+    Ring<NG, CHUNK, NWAVES, SLOTS, LEAD> ring(a.packed + (SEEDED ? a.prt : a.pstream + kSideGroups * 256), s_lds + RING0 * 256, lane, wave);
     {
         const uint32_t lbase = (uint32_t)(size_t)(__attribute__((address_space(3))) float *)s_lds;
 #pragma unroll
-        for (int i = 0; i < kSideGroups / NWAVES; i++)
-            dma_group(a.packed + a.pstream + (size_t)(i * NWAVES + wave) * 256, lbase + (uint32_t)(i * NWAVES + wave) * 1024u, (uint32_t)lane * 16u);
+        for (int i = 0; i < (SIDE + NWAVES - 1) / NWAVES; i++)
+            if (SIDE % NWAVES == 0 || i * NWAVES + wave < SIDE)
+                dma_group(a.packed + a.pstream + (size_t)(i * NWAVES + wave) * 256, lbase + (uint32_t)(i * NWAVES + wave) * 1024u, (uint32_t)lane * 16u);
+        if constexpr (RT) {                              // this wave's ray: 2 x NW direction terms behind its direction tile
+            const float *g = a.dir_bias + (size_t)ray * a.dstride + 32;
+#pragma unroll
+            for (int q = 0; q < 2; q++)
+                dma_group(g + q * 256, lbase + (uint32_t)((kSideUsed + 2 * wave + q) * 1024), (uint32_t)lane * 16u);
+        }
     }
+    // accumulator seeds of output tile T of composed layer L (0: A, 1: B): the ray's direction terms, 16 per lane
+    const float *seeds = RT ? s_lds + (kSideUsed + 2 * wave) * 256 + h * 16
+                            : a.dir_bias + (SEEDED ? (size_t)ray_index(a, b) * a.dstride + 32 + h * 16 : 0);
+    auto seed = [&](f32x16 &acc_, int L, int T) {
+        if constexpr (SEEDED) {
+            const float4 *ps = reinterpret_cast<const float4 *>(seeds + (L * NTW + T) * 32);
+#pragma unroll
+            for (int r4 = 0; r4 < 4; r4++) {
+                const float4 v = ps[r4];
+                acc_[4 * r4 + 0] = v.x; acc_[4 * r4 + 1] = v.y; acc_[4 * r4 + 2] = v.z; acc_[4 * r4 + 3] = v.w;
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc_[r] = 0.0f;                      // biases ride in the direction tile
+        }
+    };
     UCN_STAMP8(0);
     rstatic_for<LEAD>([&](auto c) { ring.template issue_chunk<c.value>(); });
     UCN_STAMP8(1);
@@ -526,8 +645,10 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void k_field_mlp_h8(MlpArgs a) {
     // (r05) the direction tile's loads are PINNED as landed here, at the top where the stream is only just starting: left to the compiler
     // their wait sits in front of the tile's first use, behind the density stage -- a `s_waitcnt vmcnt(3..0)` that, counted against a
     // hardware counter full of LDS-DMA pieces the compiler cannot see, drained the whole weight look-ahead once per pass
+    if constexpr (!SEEDED) {
 #pragma unroll
-    for (int r = 0; r < 16; r++) asm volatile("" : "+v"(ev[r]));
+        for (int r = 0; r < 16; r++) asm volatile("" : "+v"(ev[r]));
+    }
     const float in_scale = side[129];
 
     f32x16 acc[2];
@@ -563,21 +684,21 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void k_field_mlp_h8(MlpArgs a) {
         if (live && h == 0 && a.idx == nullptr) a.density[oi] = softplus(raw + a.density_bias);
     }
     UCN_STAMP8(3);
-    HPair in[3];
+    HPair in[NI];
 #pragma unroll
     for (int s = 0; s < 2; s++) {
         split_half<true>(acc[0], s, in[0]);
         split_half<true>(acc[1], s, in[1]);
-        split_half<false>(ev, s, in[2]);
+        if constexpr (!SEEDED) split_half<false>(ev, s, in[2]);
     }
     UCN_STAMP8(4);
     HPair h1s[NTW];
     rstatic_for<NP>([&](auto pc) {
         constexpr int p = pc.value;
-#pragma unroll
-        for (int r = 0; r < 16; r++) acc[0][r] = acc[1][r] = 0.0f;
-        rstatic_for<6>([&](auto ic) {
-            constexpr int i = ic.value, G = GA + (p * 6 + i) * 4;
+        seed(acc[0], 0, 2 * p);
+        seed(acc[1], 0, 2 * p + 1);
+        rstatic_for<2 * NI>([&](auto ic) {
+            constexpr int i = ic.value, G = GA + (p * 2 * NI + i) * 4;
             dstep_d<G, NG>(acc[0], acc[1], in[i / 2].hi[i % 2], in[i / 2].lo[i % 2], pipe, ring);
         });
 #pragma unroll
@@ -590,14 +711,14 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void k_field_mlp_h8(MlpArgs a) {
     float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
     rstatic_for<NP>([&](auto pc) {
         constexpr int p = pc.value;
-#pragma unroll
-        for (int r = 0; r < 16; r++) acc[0][r] = acc[1][r] = 0.0f;
-        rstatic_for<6>([&](auto ic) {
+        seed(acc[0], 1, 2 * p);
+        seed(acc[1], 1, 2 * p + 1);
+        rstatic_for<2 * NI>([&](auto ic) {
             constexpr int i = ic.value, G = GB + p * PB + i * 4;
             dstep_d<G, NG>(acc[0], acc[1], in[i / 2].hi[i % 2], in[i / 2].lo[i % 2], pipe, ring);
         });
         rstatic_for<2 * NTW>([&](auto ic) {
-            constexpr int i = ic.value, G = GB + p * PB + 24 + i * 4;
+            constexpr int i = ic.value, G = GB + p * PB + NI * 8 + i * 4;
             dstep_d<G, NG>(acc[0], acc[1], h1s[i / 2].hi[i % 2], h1s[i / 2].lo[i % 2], pipe, ring);
         });
         UCN_STAMP8(6 + 2 * p);
@@ -649,21 +770,33 @@ int ucn_h_pack(const ucn_field_t *f, const PackPlan &pl, hipStream_t st) {
                            row_tile0, nto, nti, exps, e_out, e_lo, split_col, kDirExp, reinterpret_cast<_Float16 *>(stream + g * 256));
         g += (uint64_t)nto * nti * 4;
     };
-    hipLaunchKernelGGL(k_pack_first_s, dim3(ucn_div_up(2ull * kFirstSteps * 1024, 256)), dim3(256), 0, st, f->w_d0, pl.F,
-                       kFirstSteps, exps, reinterpret_cast<_Float16 *>(stream));
-    g += 2 * kFirstSteps * 2;                                            // S0
-    pairs(MA, kCompCols, 0, pl.NTW, 3, E_H1, E_H0, 64u);                 // A: all pairs, [otp][it][s][o2]
-    for (uint32_t otp = 0; otp < pl.NTW / 2; otp++) {                    // B: per output pair
-        pairs(MB, kCompCols, 2 * otp, 2, 3, E_H2, E_H0, 64u);
-        pairs(f->w_c1, NW + NB + ND, 2 * otp, 2, pl.NTW, E_H2, E_H1, 0xFFFFFFFFu);
+    // n_in = 3: with the direction tile;  n_in = 2: the ray-tile stream (the same first layer, A and B over h0 only)
+    for (uint32_t n_in = 3; n_in >= (pl.rt_group ? 2u : 3u); n_in--) {
+        const uint64_t g_first = n_in == 3 ? 0 : pl.rt_group - kSideGroups;
+        g = g_first;
+        hipLaunchKernelGGL(k_pack_first_s, dim3(ucn_div_up(2ull * kFirstSteps * 1024, 256)), dim3(256), 0, st, f->w_d0, pl.F,
+                           kFirstSteps, exps, reinterpret_cast<_Float16 *>(stream + g * 256));
+        g += 2 * kFirstSteps * 2;                                            // S0
+        pairs(MA, kCompCols, 0, pl.NTW, n_in, E_H1, E_H0, 64u);              // A: all pairs, [otp][it][s][o2]
+        for (uint32_t otp = 0; otp < pl.NTW / 2; otp++) {                    // B: per output pair
+            pairs(MB, kCompCols, 2 * otp, 2, n_in, E_H2, E_H0, 64u);
+            pairs(f->w_c1, NW + NB + ND, 2 * otp, 2, pl.NTW, E_H2, E_H1, 0xFFFFFFFFu);
+        }
+        UCN_REQUIRE(g - g_first == stream_groups_h(pl.NTW, n_in), "field_pack: internal stream length mismatch (%llu)", (unsigned long long)g);
     }
-    UCN_REQUIRE(g == stream_groups_h(pl.NTW), "field_pack: internal stream length mismatch (%llu)", (unsigned long long)g);
     UCN_LAUNCH_CHECK("field_pack (split-f16)");
     return 0;
 }
 
-int ucn_h_dir_enc(const ucn_field_t *f, const float *viewdirs, uint32_t N, float *out, hipStream_t st) {
-    hipLaunchKernelGGL(k_dir_enc, dim3(ucn_div_up((uint64_t)N * 32, 256)), dim3(256), 0, st, viewdirs, f->n_dir, N, out);
+int ucn_h_dir_enc(const ucn_field_t *f, const PackPlan &pl, const float *viewdirs, uint32_t N, float *out, hipStream_t st) {
+    if (dir_stride_h(f->n_width) != 32) {               // 256-wide: direction tile + the ray's direction terms (needs the packed copy)
+        UCN_REQUIRE(f->packed, "field_dir_bias: mlp_mode 1 reads the composed matrices of ucn_field_pack (packed is null)");
+        const float *MA = f->packed + pl.pcomp, *MB = MA + (size_t)f->n_width * kCompCols;
+        const int *exps = reinterpret_cast<const int *>(MB + (size_t)f->n_width * kCompCols + 1);
+        hipLaunchKernelGGL(k_dir_terms, dim3(ucn_div_up(N, 32)), dim3(256), 0, st, viewdirs, MA, MB, exps, f->n_dir, N, out);
+    } else {
+        hipLaunchKernelGGL(k_dir_enc, dim3(ucn_div_up((uint64_t)N * 32, 256)), dim3(256), 0, st, viewdirs, f->n_dir, N, out);
+    }
     UCN_LAUNCH_CHECK("field_dir_bias (split-f16)");
     return 0;
 }
@@ -703,15 +836,37 @@ int ucn_h_launch(const PackPlan &pl, const MlpArgs &a, dim3 grid, hipStream_t st
     // alone, 33 + 2.6 per VALU instruction behind it), and the two waves of ONE workgroup move in lockstep between the
     // ring's barriers.  UCN_MLP_WAVES = 8 / 1: the 8-wave and the one-workgroup-per-CU kernels (experiments).
     static const int waves = getenv("UCN_MLP_WAVES") ? atoi(getenv("UCN_MLP_WAVES")) : 4;
+    // ray tiles (comment 6 at the top of the file): UCN_MLP_RAY_TILE=0 keeps every launch on the [any rays][32] tile (the A/B)
+    const char *rt_env = getenv("UCN_MLP_RAY_TILE");                          // read per call: one process can hold both kernels to each other
+    const bool ray_tiles = !(rt_env && atoi(rt_env) == 0);
+    // a batch of whole 32-sample ray tiles: the plain launch runs MODE 1, and what must agree with it bit for bit (compacted colour
+    // pass, co-resident shape) MODE 2.  Every other shape (samples_per_ray % 32 != 0, 64-wide fields, density-only) is untouched.
+    const bool tiles_ok = a.rgb != nullptr && pl.NTW == 8 && waves == 4 && ray_tiles && a.spr % 32u == 0u && a.B == a.n_rays * a.spr;
+    MlpArgs rt = a;
+    rt.prt = a.pstream + (uint64_t)pl.rt_group * 256;
+    if (tiles_ok && (a.small_ring || a.idx != nullptr)) {
+        hipLaunchKernelGGL((k_field_mlp_h8<8, 4, UCN_MLP2_CHUNK, UCN_MLP2_SLOTS, UCN_MLP2_LEAD, UCN_MLP8_DEPTH, 2>), grid, dim3(256),
+                           (kSideGroups + UCN_MLP2_SLOTS * UCN_MLP2_CHUNK) * 1024, st, rt);
+        UCN_LAUNCH_CHECK("field_mlp (split-f16, per-lane direction terms)");
+        return 0;
+    }
+    if (tiles_ok) {
+        const uint32_t tiles = a.spr / 32u;
+        const dim3 grid_rt(a.rays_fastest ? ucn_div_up(a.n_rays, 4) * tiles : ucn_div_up((uint64_t)a.n_rays * tiles, 4));
+        hipLaunchKernelGGL((k_field_mlp_h8<8, 4, UCN_MLP2_CHUNK, UCN_MLP2_SLOTS, UCN_MLP2_LEAD, UCN_MLP8_DEPTH, 1>), grid_rt, dim3(256),
+                           (kRtLdsGroups + UCN_MLP2_SLOTS * UCN_MLP2_CHUNK) * 1024, st, rt);
+        UCN_LAUNCH_CHECK("field_mlp (split-f16, ray tiles)");
+        return 0;
+    }
     if (a.rgb != nullptr && pl.NTW == 8 && !a.small_ring && waves == 8) {
         const dim3 grid8(ucn_div_up(a.B, 256));
-        hipLaunchKernelGGL((k_field_mlp_h8<8, 8, UCN_MLP8_CHUNK, UCN_MLP8_SLOTS, UCN_MLP8_LEAD, UCN_MLP8_DEPTH>), grid8, dim3(512),
+        hipLaunchKernelGGL((k_field_mlp_h8<8, 8, UCN_MLP8_CHUNK, UCN_MLP8_SLOTS, UCN_MLP8_LEAD, UCN_MLP8_DEPTH, 0>), grid8, dim3(512),
                            (kSideGroups + UCN_MLP8_SLOTS * UCN_MLP8_CHUNK) * 1024, st, a);
         UCN_LAUNCH_CHECK("field_mlp (split-f16, 8 waves)");
         return 0;
     }
     if (a.rgb != nullptr && pl.NTW == 8 && (waves == 4 || a.small_ring)) {     // (also the co-resident shape: 72 KiB, 254 registers)
-        hipLaunchKernelGGL((k_field_mlp_h8<8, 4, UCN_MLP2_CHUNK, UCN_MLP2_SLOTS, UCN_MLP2_LEAD, UCN_MLP8_DEPTH>), grid, dim3(256),
+        hipLaunchKernelGGL((k_field_mlp_h8<8, 4, UCN_MLP2_CHUNK, UCN_MLP2_SLOTS, UCN_MLP2_LEAD, UCN_MLP8_DEPTH, 0>), grid, dim3(256),
                            (kSideGroups + UCN_MLP2_SLOTS * UCN_MLP2_CHUNK) * 1024, st, a);
         UCN_LAUNCH_CHECK("field_mlp (split-f16, 2 workgroups per CU)");
         return 0;

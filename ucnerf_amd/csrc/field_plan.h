@@ -8,6 +8,7 @@
 struct PackPlan {
     uint64_t p0, pstream, phead, pcomp, total;        // float offsets into ucn_field_t::packed
     uint32_t F, KQ, NTB, NTW, n_groups;               // n_groups: weight-stream length of the ACTIVE mode
+    uint32_t rt_group;                                // mode 1, 256-wide: first group (from pstream) of the ray-tile stream, else 0
     bool prop;
 };
 
@@ -20,9 +21,17 @@ static inline uint32_t stream_groups_f32(uint32_t NTB, uint32_t NTW) {
 // then the NTW hidden tiles).  A side table of kSideGroups groups sits in front of it.
 constexpr uint32_t kFirstSteps = 4;                   // first layer: F <= 16*kFirstSteps inputs (zero padded)
 constexpr uint32_t kCompCols = 96;                    // composed layers: [64 hidden | 27 direction | bias | 0...]
-static inline uint32_t stream_groups_h(uint32_t NTW) {
-    return 4 * (kFirstSteps + 3 * NTW + NTW * (3 + NTW));
+// n_in = 3: the stream of the kernels whose tile is 32 samples of any rays (the direction tile is the third input tile);
+// n_in = 2: the ray-tile stream (field_mlp_h.hip comment 6: the direction terms are per-ray accumulator seeds)
+static inline uint32_t stream_groups_h(uint32_t NTW, uint32_t n_in = 3) {
+    return 4 * (kFirstSteps + n_in * NTW + NTW * (n_in + NTW));
 }
+static inline uint32_t ring_padded(uint32_t groups) {           // + slack: the prologue's DMA may run past a short stream
+    return (groups + kRingPad - 1) / kRingPad * kRingPad + kRingPad;
+}
+// mode 1: floats per ray of the buffer ucn_field_dir_bias writes: the 32-wide direction tile, and for 256-wide fields
+// behind it the ray's 2 x NW direction terms in accumulator-slot order
+static inline uint32_t dir_stride_h(uint32_t n_width) { return n_width == 256 ? 32 + 2 * n_width : 32; }
 
 static inline int make_plan(const ucn_field_t *f, PackPlan *pl) {
     UCN_REQUIRE(f, "field: null descriptor");
@@ -38,7 +47,7 @@ static inline int make_plan(const ucn_field_t *f, PackPlan *pl) {
     o = (o + 255) & ~255ull;                           // keep the stream 1 KiB aligned
     if (pl->prop) {
         pl->NTB = pl->NTW = 0;
-        pl->n_groups = 0;
+        pl->n_groups = pl->rt_group = 0;
         pl->pstream = o;
         pl->phead = o; o += 64;
         pl->pcomp = o;
@@ -53,7 +62,8 @@ static inline int make_plan(const ucn_field_t *f, PackPlan *pl) {
         pl->NTB = f->n_bottleneck / 32;
         pl->NTW = f->n_width / 32;
         const uint32_t g0 = (stream_groups_f32(pl->NTB, pl->NTW) + kChunkGroups - 1) / kChunkGroups * kChunkGroups;
-        const uint32_t g1 = kSideGroups + (stream_groups_h(pl->NTW) + kRingPad - 1) / kRingPad * kRingPad + kRingPad;   // + slack: the prologue's DMA may run past a short stream
+        pl->rt_group = pl->NTW == 8 ? kSideGroups + ring_padded(stream_groups_h(pl->NTW)) : 0;
+        const uint32_t g1 = kSideGroups + ring_padded(stream_groups_h(pl->NTW)) + (pl->NTW == 8 ? ring_padded(stream_groups_h(pl->NTW, 2)) : 0);
         pl->n_groups = f->mlp_mode == 1 ? g1 : g0;
         pl->pstream = o; o += (uint64_t)(g0 > g1 ? g0 : g1) * 256;
         pl->phead = o; o += (uint64_t)pl->NTW * 128;
@@ -67,12 +77,15 @@ struct MlpArgs {
     const float *feat;        // [L][B][C]
     const float *packed;
     const float *b_d0, *b_d1, *b_c0, *b_c1, *b_rgb;
-    const float *dir_bias;    // mode 0: [rays][2][NW] per-ray biases; mode 1: [rays][32] direction encoding + 1.0
+    const float *dir_bias;    // mode 0: [rays][2][NW] per-ray biases; mode 1: [rays][dstride]: direction encoding + 1.0 (32 floats),
+    //                           then, 256-wide fields, the ray's direction terms [layer][tile][h][16] on the accumulators' scale
     float *density, *rgb, *bott;
     uint32_t B, spr, C, F, n_chunks;
     uint32_t cshift;                 // log2(C) when C is 1, 2, 4 or 8 and the features span < 4 GiB (load_features), else 0xFF
     uint32_t n_rays, rays_fastest;   // rays_fastest: feature index b = s*n_rays + ray (else ray*spr + s)
     uint32_t small_ring;             // mode 1: 64 KiB weight ring (co-resident launches)
+    uint32_t dstride;                // mode 1: floats per ray of dir_bias (dir_stride_h)
+    uint64_t prt;                    // mode 1: float offset of the ray-tile stream in `packed` (set by ucn_h_launch)
     const uint32_t *idx, *count;     // compacted colour pass: tile slot i evaluates sample idx[i], i < *count (else NULL)
     uint64_t p0, pstream, phead;
     float density_bias, rgb_premult, rgb_bias, rgb_padding;
@@ -154,5 +167,5 @@ __device__ __forceinline__ void rgb_head(const f32x16 (&h2)[NTW], const MlpArgs 
 
 // implemented in field_mlp_h.hip
 int ucn_h_pack(const ucn_field_t *f, const PackPlan &pl, hipStream_t st);
-int ucn_h_dir_enc(const ucn_field_t *f, const float *viewdirs, uint32_t N, float *out, hipStream_t st);
+int ucn_h_dir_enc(const ucn_field_t *f, const PackPlan &pl, const float *viewdirs, uint32_t N, float *out, hipStream_t st);
 int ucn_h_launch(const PackPlan &pl, const MlpArgs &a, dim3 grid, hipStream_t st);
