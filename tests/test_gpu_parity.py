@@ -1278,8 +1278,8 @@ def test_sky_split_f16_range(case):
     guard of test_split_f16_range did not cover it.  It now carries statistical power-of-two scales chosen at pack time
     (sky.hip k_sky_scales): whatever the magnitudes of the trunk's activations -- 1e-4 (low halves would be subnormal),
     1e5 (f16 operands would overflow to inf), or alternating from layer to layer -- the rendered sky colour must stay
-    fp32-class against a float64 evaluation of the same network (train_graph.sky_forward on a double copy).  With the scales
-    switched off (UCN_SKY_NO_SCALES=1) `tiny_trunk` is 1.8e-5 and `huge_trunk` 6.8e-5 off -- 100x / 400x the float32 reference's
+    fp32-class against a float64 evaluation of the same network (train_graph.sky_forward on a double copy).  In a build
+    without the scales (every exponent 0) `tiny_trunk` is 1.8e-5 and `huge_trunk` 6.8e-5 off -- 100x / 400x the float32 reference's
     own 1.7e-7 -- and both cases fail this test."""
     import copy
     from ucnerf_amd.internal import train_graph as tg

@@ -883,7 +883,7 @@ def test_fused_sky_training_kernels_match_the_eager_graph(n):
             if p.dim() == 1:
                 p.normal_(0, 0.1)
     # n = 1003: 120 360 samples = 940 workgroups of 128 + 40 -- a ragged tile and two dead waves in the last workgroup (their
-    # conditional stores do not issue: Ring::count_stores), and the two-tile variant's last workgroup half empty
+    # conditional stores do not issue)
     g = torch.Generator().manual_seed(6)
     rays = rm.synthetic_rays(n, seed=12)
     o, d, cam = (rays[k].cuda() for k in ("origins", "directions", "cam_dirs"))
@@ -918,39 +918,6 @@ def test_fused_sky_training_kernels_match_the_eager_graph(n):
         assert f_k <= max(1.5 * e_k, 3e-2) and cos >= min(0.995, cos_e - 2e-3), (k, f_k, e_k, cos, cos_e)
         worst = max(worst, f_k / max(e_k, 1e-3))
     print(f"fused sky: output rel {f_out:.2e} (eager autocast {e_out:.2e}); worst gradient ratio fused / eager = {worst:.2f}")
-
-
-@pytest.mark.gpu
-@pytest.mark.parametrize("n", [1024, 77])
-def test_sky_forward_two_tile_variant_is_bit_identical(n, monkeypatch):
-    """UCN_SKY_FWD_TILES=2 (csrc/sky_train.hip k_sky_train_fwd2: two sample tiles per wave, the MFMA's register classes written by
-    hand, the MFMA -> VALU and VALU -> MFMA wait states placed by hand) against the default kernel: every buffer the backward
-    consumes -- raw, the bf16 activations, the ReLU mask words -- and the composited colour, bit for bit."""
-    from ucnerf_amd.internal import train_graph as tg
-    from ucnerf_amd.internal.sky import NeRF
-    torch.manual_seed(5)
-    net = NeRF(D=8, d_in_view=3, W=256, multires_view=4, output_ch=4, skips=[4]).cuda()
-    with torch.no_grad():
-        for p in net.parameters():
-            if p.dim() == 1:
-                p.normal_(0, 0.1)
-    rays = rm.synthetic_rays(n, seed=12)
-    o, d, cam = (rays[k].cuda() for k in ("origins", "directions", "cam_dirs"))
-    far = rays["far"].cuda()
-    got = {}
-    for tiles in ("1", "2"):
-        monkeypatch.setenv("UCN_SKY_FWD_TILES", tiles)
-        with torch.autocast("cuda", dtype=torch.bfloat16):
-            out = tg.sky_forward_fused(net, o, d, cam, far)
-        torch.cuda.synchronize()
-        fn = out.grad_fn
-        while fn is not None and "SkyFused" not in type(fn).__name__:
-            fn = fn.next_functions[0][0] if fn.next_functions else None
-        packed, raw, d_, far_, act, mask, mask_v = fn.saved_tensors
-        used = 2048 + 32 + 128                                   # h0 .. h7 | aux | hv; the row's last 32 columns are padding
-        got[tiles] = (out.detach().clone(), raw.clone(), act[:, :used].clone(), mask.clone(), mask_v.clone())
-    for name, a, b in zip(("sky_rgb", "raw", "act", "mask", "mask_v"), got["1"], got["2"]):
-        assert torch.equal(a, b), (name, int((a != b).sum()), tuple(a.shape))
 
 
 @pytest.mark.gpu

@@ -9,7 +9,7 @@ inside its chain); 12 drains in k_train_fwd (bias / per-ray loads inside the cha
 import glob, os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "ucnerf_amd", "csrc")
-NOSLP = {"field_mlp", "field_mlp_h", "sky", "sky_train", "field_train", "wgrad", "gemm_f32"}
+NOSLP = {"field_mlp", "field_mlp_h", "sky", "sky_train", "field_train", "wgrad", "gemm_f32", "gemm_h3"}
 files = [os.path.splitext(os.path.basename(f))[0] for f in (sys.argv[1:] or sorted(glob.glob(os.path.join(CSRC, "*.hip"))))]
 tmp = tempfile.mkdtemp()
 base = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-w"]

@@ -1,7 +1,7 @@
 """Time ucn_field_mlp alone on the benchmark NeRF field (random features, 65536 rays x 128 samples).
 
 usage: python tools/mlp_bench.py [--lib path/to/libucnerf_march.so] [--mode 0|1] [--rays-fastest] [--iters 5]
-The --lib override is for experiment builds (tools/build_exp.sh); the product always loads the in-tree library.
+The --lib override loads another build of the same ABI; the product always loads the in-tree library.
 """
 import argparse, ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

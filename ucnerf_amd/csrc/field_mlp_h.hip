@@ -324,31 +324,8 @@ __device__ __forceinline__ void head_eighth(const f32x16 (&pair)[2], const float
     head_quarter<T0 + E / 4, E % 4>(pair[E / 4], side, h, s0, s1, s2);
 }
 
-#ifdef UCN_EXP_STOP        // experiment builds: leave the kernel after a phase (timing by difference; results are garbage)
-#define UCN_STOP_AT(k, accpair)                                                                       \
-    do {                                                                                              \
-        if constexpr (UCN_EXP_STOP == (k)) {                                                          \
-            float keep = 0.0f;                                                                        \
-            for (int r = 0; r < 16; r++) keep += accpair[0][r] + accpair[1][r];                       \
-            if (live && h == 0) a.rgb[(size_t)oi * 3] = keep;                                         \
-            ring.drain();                                                                             \
-            __syncthreads();                                                                          \
-            return;                                                                                   \
-        }                                                                                             \
-    } while (0)
-#else
-#define UCN_STOP_AT(k, accpair) do { } while (0)
-#endif
-#ifdef UCN_EXP_TIMING      // experiment builds: s_memtime stamps of workgroup 64's wave 0 into the (otherwise unused) bottleneck buffer
-#define UCN_STAMP(i) do { if (blockIdx.x == UCN_EXP_TIMING && threadIdx.x == 0) a.bott[i] = (float)(__builtin_readcyclecounter() - t_begin); } while (0)
-#else
-#define UCN_STAMP(i) do { } while (0)
-#endif
-template <int NTW, bool RGB, int CHUNK, int STAGE>
+template <int NTW, bool RGB, int CHUNK>
 __global__ __launch_bounds__(256) void k_field_mlp_h(MlpArgs a) {
-#ifdef UCN_EXP_TIMING
-    const unsigned long long t_begin = __builtin_readcyclecounter();
-#endif
     extern __shared__ __attribute__((aligned(16))) float s_lds[];   // [side table][ring]
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -386,7 +363,7 @@ __global__ __launch_bounds__(256) void k_field_mlp_h(MlpArgs a) {
     }
     // ---- weight DMA: side table, then the first kLead chunks of the ring
     const float *side = s_lds;
-    Ring<NG, CHUNK, 4, kRingSlots, kLead, STAGE> ring(a.packed + a.pstream + kSideGroups * 256, s_lds + kSideGroups * 256, lane, wave);
+    Ring<NG, CHUNK, 4, kRingSlots, kLead> ring(a.packed + a.pstream + kSideGroups * 256, s_lds + kSideGroups * 256, lane, wave);
     {
         const uint32_t lbase = (uint32_t)(size_t)(__attribute__((address_space(3))) float *)s_lds;
 #pragma unroll
@@ -394,10 +371,7 @@ __global__ __launch_bounds__(256) void k_field_mlp_h(MlpArgs a) {
             dma_group(a.packed + a.pstream + (size_t)(i * 4 + wave) * 256, lbase + (uint32_t)(i * 4 + wave) * 1024u, (uint32_t)lane * 16u);
     }
     rstatic_for<kLead>([&](auto c) { ring.template issue_chunk<c.value>(); });
-    UCN_STAMP(0);
-    if constexpr (STAGE > 0) ring.drain();          // the side table came by DMA
     ring.template boundary<0>();                    // side table + chunk 0 landed (the later chunks stay in flight)
-    UCN_STAMP(1);
     if constexpr (RGB) {
         // (r05) the direction tile's loads are PINNED as landed here, at the top where the stream is only just starting: left to the compiler
         // their wait sits in front of the tile's first use, behind the density stage -- a `s_waitcnt vmcnt(3..0)` that, counted against a
@@ -431,9 +405,7 @@ __global__ __launch_bounds__(256) void k_field_mlp_h(MlpArgs a) {
         rstatic_for<kKS>([&](auto s) { dstep<4 * s.value, NG>(acc0[0], acc0[1], fhi[s.value], flo[s.value], pipe, ring); });
         relu_tile(acc0[0]);
         relu_tile(acc0[1]);
-        UCN_STAMP(2);
     }
-    if constexpr (RGB) UCN_STOP_AT(1, acc0);
     // ---- raw density = row 0 of the second density layer, on the VALU (models.py:508,581): this lane holds
     //      32 of the 64 hidden units of its sample
     {
@@ -454,7 +426,6 @@ __global__ __launch_bounds__(256) void k_field_mlp_h(MlpArgs a) {
             split_half<false>(acc0[1], s, in[1]);
             split_half<false>(ev, s, in[2]);
         }
-        UCN_STAMP(3);
         // ---- A: composed colour layer 0, pair by pair; pair p - 1 is ReLU'd and split under pair p's MFMAs
         HPair h1s[NTW];
         f32x16 acc[2][2];                                    // pair q of the whole program lives in acc[q % 2]
@@ -471,8 +442,6 @@ __global__ __launch_bounds__(256) void k_field_mlp_h(MlpArgs a) {
                     dstep<G, NG>(acc[p % 2][0], acc[p % 2][1], in[i / 2].hi[i % 2], in[i / 2].lo[i % 2], pipe, ring);
             });
         });
-        UCN_STOP_AT(2, acc[(NP - 1) % 2]);
-        UCN_STAMP(4);
         // ---- B: colour layer 1, pair by pair: skip part (reads `in`), then the hidden part (reads h1s).  Under the skip
         //      part's MFMAs: the split of A's last pair (p = 0) or the rgb head of pair p - 1
         float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
@@ -491,7 +460,6 @@ __global__ __launch_bounds__(256) void k_field_mlp_h(MlpArgs a) {
                 else
                     dstep<G, NG>(acc[qp][0], acc[qp][1], in[i / 2].hi[i % 2], in[i / 2].lo[i % 2], pipe, ring);
             });
-            UCN_STAMP(5 + 2 * p);
             rstatic_for<2 * NTW>([&](auto ic) {                                           // [it < NTW][s]
                 constexpr int i = ic.value, G = GB + p * PB + 24 + i * 4;
                 if constexpr (p > 0 && i < 2)
@@ -500,11 +468,8 @@ __global__ __launch_bounds__(256) void k_field_mlp_h(MlpArgs a) {
                 else
                     dstep<G, NG>(acc[qp][0], acc[qp][1], h1s[i / 2].hi[i % 2], h1s[i / 2].lo[i % 2], pipe, ring);
             });
-            UCN_STOP_AT(3 + p, acc[qp]);
         });
-        UCN_STAMP(13);
         rstatic_for<8>([&](auto e) { head_eighth<2 * (NP - 1), e.value>(acc[(2 * NP - 1) % 2], side, h, s0, s1, s2); });
-        UCN_STAMP(14);
         // ---- rgb: sigmoid + padding (models.py:657-674)
         s0 = xor32_sum(s0);
         s1 = xor32_sum(s1);
@@ -523,20 +488,20 @@ __global__ __launch_bounds__(256) void k_field_mlp_h(MlpArgs a) {
 }
 
 
-// ---- 8-wave variant: 512-thread workgroups, TWO waves per SIMD, 256 samples per pass over the weight stream.
-// k_field_mlp_h above streams 464 KiB of weights through LDS per 128 samples, and the LDS-DMA path lands ~10 B per
-// clock and CU (25 GB/s: cycle stamps in profiles/r02*/mlp_timeline.txt; the same figure as MI355X_MICROARCH.md's
-// "ldsdma-fill" row): 4 KiB per double step = 393 cycles where the six MFMAs need 192 -- the kernel sits at that floor.
-// Here eight waves share the stream, so the DMA moves half the bytes per sample and the two waves of a SIMD take turns
-// on the matrix pipe: one computes while the other splits / runs the rgb head / waits for LDS.  That needs <= 256
-// registers per lane: ONE accumulator pair, nothing in MFMA shadows (the partner wave is the shadow), a short
-// operand pipe.
+// ---- the 256-wide colour field: <= 256 registers per lane, so that TWO waves share a SIMD (4-wave workgroups, two per CU).
+// k_field_mlp_h above would stream 464 KiB of weights through LDS per 128 samples with one wave per SIMD, and the LDS-DMA path lands
+// ~10 B per clock and CU (25 GB/s: cycle stamps in profiles/r02*/mlp_timeline.txt; the same figure as MI355X_MICROARCH.md's
+// "ldsdma-fill" row): 4 KiB per double step = 393 cycles where the six MFMAs need 192.  Here the two waves of a SIMD take turns
+// on the matrix pipe: one computes while the other splits / runs the rgb head / waits for LDS.  That needs ONE accumulator pair,
+// nothing in MFMA shadows (the partner wave is the shadow), a short operand pipe.
 //
 // Ray tiles (MODE 1; comment 6 at the top; NWAVES = 4, no compaction list, samples_per_ray % 32 == 0): a wave's tile is 32 consecutive samples of
 // one ray.  Rays-fastest features: workgroup = 4 neighbouring rays x the same 32 samples, workgroups ray-group-fastest; otherwise the
 // plain tile order (a [ray][sample] batch's tiles ARE ray tiles).  LDS: [side table, kSideUsed groups][4 x 2 KiB direction terms][ring].
 constexpr int kSideUsed = 5;                         // groups of the side table that hold anything (floats [0, 1280))
 constexpr int kRtLdsGroups = kSideUsed + 8;          // ray-tile kernel: the ring starts here
+constexpr int kH8Chunk = 16, kH8Slots = 4, kH8Lead = 2;   // its 64 KiB ring (two workgroups per CU)
+constexpr int kH8Depth = 2;                          // operand pairs in flight per wave
 //
 // MODE 0: the direction tile is the third input tile (comment 3).  MODE 1: ray tiles.  MODE 2: the [any rays][32] tile with the SAME
 // arithmetic per sample as MODE 1 -- the ray-tile stream, and every lane fetches its own ray's seeds from global memory, pair by pair
@@ -546,12 +511,6 @@ constexpr int kRtLdsGroups = kSideUsed + 8;          // ray-tile kernel: the rin
 template <int NTW, int NWAVES, int CHUNK, int SLOTS, int LEAD, int DEPTH, int MODE>
 __global__ __launch_bounds__(NWAVES * 64, 2) void k_field_mlp_h8(MlpArgs a) {
     constexpr bool RT = MODE == 1, SEEDED = MODE != 0;
-#ifdef UCN_EXP_TIMING
-    const unsigned long long t_begin = __builtin_readcyclecounter();
-#define UCN_STAMP8(i) do { if (blockIdx.x == UCN_EXP_TIMING && (threadIdx.x & 255) == 0) a.bott[(threadIdx.x >> 8) * 32 + (i)] = (float)(__builtin_readcyclecounter() - t_begin); } while (0)
-#else
-#define UCN_STAMP8(i) do { } while (0)
-#endif
     extern __shared__ __attribute__((aligned(16))) float s_lds[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -637,11 +596,8 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void k_field_mlp_h8(MlpArgs a) {
             for (int r = 0; r < 16; r++) acc_[r] = 0.0f;                      // biases ride in the direction tile
         }
     };
-    UCN_STAMP8(0);
     rstatic_for<LEAD>([&](auto c) { ring.template issue_chunk<c.value>(); });
-    UCN_STAMP8(1);
     ring.template boundary<0>();
-    UCN_STAMP8(2);
     // (r05) the direction tile's loads are PINNED as landed here, at the top where the stream is only just starting: left to the compiler
     // their wait sits in front of the tile's first use, behind the density stage -- a `s_waitcnt vmcnt(3..0)` that, counted against a
     // hardware counter full of LDS-DMA pieces the compiler cannot see, drained the whole weight look-ahead once per pass
@@ -683,7 +639,6 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void k_field_mlp_h8(MlpArgs a) {
         const float raw = xor32_sum(part) + pd[64];
         if (live && h == 0 && a.idx == nullptr) a.density[oi] = softplus(raw + a.density_bias);
     }
-    UCN_STAMP8(3);
     HPair in[NI];
 #pragma unroll
     for (int s = 0; s < 2; s++) {
@@ -691,7 +646,6 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void k_field_mlp_h8(MlpArgs a) {
         split_half<true>(acc[1], s, in[1]);
         if constexpr (!SEEDED) split_half<false>(ev, s, in[2]);
     }
-    UCN_STAMP8(4);
     HPair h1s[NTW];
     rstatic_for<NP>([&](auto pc) {
         constexpr int p = pc.value;
@@ -707,7 +661,6 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void k_field_mlp_h8(MlpArgs a) {
             split_half<true>(acc[1], s, h1s[2 * p + 1]);
         }
     });
-    UCN_STAMP8(5);
     float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
     rstatic_for<NP>([&](auto pc) {
         constexpr int p = pc.value;
@@ -721,9 +674,7 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void k_field_mlp_h8(MlpArgs a) {
             constexpr int i = ic.value, G = GB + p * PB + NI * 8 + i * 4;
             dstep_d<G, NG>(acc[0], acc[1], h1s[i / 2].hi[i % 2], h1s[i / 2].lo[i % 2], pipe, ring);
         });
-        UCN_STAMP8(6 + 2 * p);
         rstatic_for<8>([&](auto e) { head_eighth<2 * p, e.value>(acc, side, h, s0, s1, s2); });
-        UCN_STAMP8(7 + 2 * p);
     });
     s0 = xor32_sum(s0);
     s1 = xor32_sum(s1);
@@ -802,72 +753,46 @@ int ucn_h_dir_enc(const ucn_field_t *f, const PackPlan &pl, const float *viewdir
 }
 
 int ucn_h_launch(const PackPlan &pl, const MlpArgs &a, dim3 grid, hipStream_t st) {
-#ifndef UCN_EXP_TIMING
     UCN_REQUIRE(a.bott == nullptr, "field_mlp: mlp_mode 1 composes the bottleneck away; request bottleneck_out with mlp_mode 0");
-#endif
     // a.small_ring: the 64 KiB ring (+ side table = 72 KiB), so that one 512-thread featurisation workgroup holding
     // 88 KiB can share the CU (DESIGN.md "Co-residency"); default: the 128 KiB ring
 #define UCN_MLP_H(NTW_, RGB_)                                                                                              \
     do {                                                                                                                   \
         if (a.small_ring)                                                                                                  \
-            hipLaunchKernelGGL((k_field_mlp_h<NTW_, RGB_, kRingChunkSmall, 0>), grid, dim3(256), ring_lds_bytes(kRingChunkSmall), st, a); \
+            hipLaunchKernelGGL((k_field_mlp_h<NTW_, RGB_, kRingChunkSmall>), grid, dim3(256), ring_lds_bytes(kRingChunkSmall), st, a); \
         else                                                                                                               \
-            hipLaunchKernelGGL((k_field_mlp_h<NTW_, RGB_, kRingChunk, UCN_MLP4_STAGE>), grid, dim3(256), ring_lds_bytes(kRingChunk), st, a); \
+            hipLaunchKernelGGL((k_field_mlp_h<NTW_, RGB_, kRingChunk>), grid, dim3(256), ring_lds_bytes(kRingChunk), st, a); \
     } while (0)
-#ifndef UCN_MLP8_DEPTH
-#define UCN_MLP8_DEPTH 2
-#endif
-#ifndef UCN_MLP4_STAGE
-#define UCN_MLP4_STAGE 0
-#endif
-#ifndef UCN_MLP8_CHUNK
-#define UCN_MLP8_CHUNK 32
-#define UCN_MLP8_SLOTS 4
-#define UCN_MLP8_LEAD 2
-#endif
-#ifndef UCN_MLP2_CHUNK          // 64 KiB ring of the two-workgroups-per-CU kernel
-#define UCN_MLP2_CHUNK 16
-#define UCN_MLP2_SLOTS 4
-#define UCN_MLP2_LEAD 2
-#endif
     // default for the 256-wide colour field: 4-wave workgroups of <= 256 registers, TWO per CU (72 KiB of LDS each), so
     // every SIMD holds two waves of DIFFERENT workgroups: one wave's MFMAs run while the other splits, reads LDS, issues
     // DMA or sits in its prologue.  Within one wave nothing overlaps an MFMA (tools/mfma_valu_bench.hip: 33 cycles per MFMA
     // alone, 33 + 2.6 per VALU instruction behind it), and the two waves of ONE workgroup move in lockstep between the
-    // ring's barriers.  UCN_MLP_WAVES = 8 / 1: the 8-wave and the one-workgroup-per-CU kernels (experiments).
-    static const int waves = getenv("UCN_MLP_WAVES") ? atoi(getenv("UCN_MLP_WAVES")) : 4;
+    // ring's barriers.  (8-wave workgroups and one workgroup per CU both lost: profiles/r06/mlp_waves_ab.txt.)
     // ray tiles (comment 6 at the top of the file): UCN_MLP_RAY_TILE=0 keeps every launch on the [any rays][32] tile (the A/B)
     const char *rt_env = getenv("UCN_MLP_RAY_TILE");                          // read per call: one process can hold both kernels to each other
     const bool ray_tiles = !(rt_env && atoi(rt_env) == 0);
     // a batch of whole 32-sample ray tiles: the plain launch runs MODE 1, and what must agree with it bit for bit (compacted colour
     // pass, co-resident shape) MODE 2.  Every other shape (samples_per_ray % 32 != 0, 64-wide fields, density-only) is untouched.
-    const bool tiles_ok = a.rgb != nullptr && pl.NTW == 8 && waves == 4 && ray_tiles && a.spr % 32u == 0u && a.B == a.n_rays * a.spr;
+    const bool tiles_ok = a.rgb != nullptr && pl.NTW == 8 && ray_tiles && a.spr % 32u == 0u && a.B == a.n_rays * a.spr;
     MlpArgs rt = a;
     rt.prt = a.pstream + (uint64_t)pl.rt_group * 256;
     if (tiles_ok && (a.small_ring || a.idx != nullptr)) {
-        hipLaunchKernelGGL((k_field_mlp_h8<8, 4, UCN_MLP2_CHUNK, UCN_MLP2_SLOTS, UCN_MLP2_LEAD, UCN_MLP8_DEPTH, 2>), grid, dim3(256),
-                           (kSideGroups + UCN_MLP2_SLOTS * UCN_MLP2_CHUNK) * 1024, st, rt);
+        hipLaunchKernelGGL((k_field_mlp_h8<8, 4, kH8Chunk, kH8Slots, kH8Lead, kH8Depth, 2>), grid, dim3(256),
+                           (kSideGroups + kH8Slots * kH8Chunk) * 1024, st, rt);
         UCN_LAUNCH_CHECK("field_mlp (split-f16, per-lane direction terms)");
         return 0;
     }
     if (tiles_ok) {
         const uint32_t tiles = a.spr / 32u;
         const dim3 grid_rt(a.rays_fastest ? ucn_div_up(a.n_rays, 4) * tiles : ucn_div_up((uint64_t)a.n_rays * tiles, 4));
-        hipLaunchKernelGGL((k_field_mlp_h8<8, 4, UCN_MLP2_CHUNK, UCN_MLP2_SLOTS, UCN_MLP2_LEAD, UCN_MLP8_DEPTH, 1>), grid_rt, dim3(256),
-                           (kRtLdsGroups + UCN_MLP2_SLOTS * UCN_MLP2_CHUNK) * 1024, st, rt);
+        hipLaunchKernelGGL((k_field_mlp_h8<8, 4, kH8Chunk, kH8Slots, kH8Lead, kH8Depth, 1>), grid_rt, dim3(256),
+                           (kRtLdsGroups + kH8Slots * kH8Chunk) * 1024, st, rt);
         UCN_LAUNCH_CHECK("field_mlp (split-f16, ray tiles)");
         return 0;
     }
-    if (a.rgb != nullptr && pl.NTW == 8 && !a.small_ring && waves == 8) {
-        const dim3 grid8(ucn_div_up(a.B, 256));
-        hipLaunchKernelGGL((k_field_mlp_h8<8, 8, UCN_MLP8_CHUNK, UCN_MLP8_SLOTS, UCN_MLP8_LEAD, UCN_MLP8_DEPTH, 0>), grid8, dim3(512),
-                           (kSideGroups + UCN_MLP8_SLOTS * UCN_MLP8_CHUNK) * 1024, st, a);
-        UCN_LAUNCH_CHECK("field_mlp (split-f16, 8 waves)");
-        return 0;
-    }
-    if (a.rgb != nullptr && pl.NTW == 8 && (waves == 4 || a.small_ring)) {     // (also the co-resident shape: 72 KiB, 254 registers)
-        hipLaunchKernelGGL((k_field_mlp_h8<8, 4, UCN_MLP2_CHUNK, UCN_MLP2_SLOTS, UCN_MLP2_LEAD, UCN_MLP8_DEPTH, 0>), grid, dim3(256),
-                           (kSideGroups + UCN_MLP2_SLOTS * UCN_MLP2_CHUNK) * 1024, st, a);
+    if (a.rgb != nullptr && pl.NTW == 8) {     // (also the co-resident shape: 72 KiB, 254 registers)
+        hipLaunchKernelGGL((k_field_mlp_h8<8, 4, kH8Chunk, kH8Slots, kH8Lead, kH8Depth, 0>), grid, dim3(256),
+                           (kSideGroups + kH8Slots * kH8Chunk) * 1024, st, a);
         UCN_LAUNCH_CHECK("field_mlp (split-f16, 2 workgroups per CU)");
         return 0;
     }
@@ -875,8 +800,7 @@ int ucn_h_launch(const PackPlan &pl, const MlpArgs &a, dim3 grid, hipStream_t st
         if (pl.NTW == 8) UCN_MLP_H(8, false);
         else UCN_MLP_H(2, false);
     } else {
-        if (pl.NTW == 8) UCN_MLP_H(8, true);
-        else UCN_MLP_H(2, true);
+        UCN_MLP_H(2, true);
     }
 #undef UCN_MLP_H
     UCN_LAUNCH_CHECK("field_mlp (split-f16)");

@@ -45,44 +45,15 @@ struct TrainFwdArgs {
 };
 
 
-// UCN_TRAIN_OCC: workgroups per CU both kernels are cut for (build knob); the ring follows it (two per CU: 4 x 16 KiB, 2 chunks ahead;
-// one per CU: 6 x 16 KiB, 4 ahead)
-#ifndef UCN_TRAIN_OCC
-#define UCN_TRAIN_OCC 2
-#endif
-// UCN_TRAIN_WAVES: waves per workgroup of the two training kernels (4: two workgroups per CU; 8: ONE workgroup per CU whose eight waves
-// share one ring -- half the LDS-DMA weight stream per sample, a 6-slot ring, still two waves per SIMD)
-#ifndef UCN_TRAIN_WAVES
-#define UCN_TRAIN_WAVES 8
-#endif
-constexpr int kTrainWaves = UCN_TRAIN_WAVES;
-// UCN_TRAIN_STAGED (r05): activation / gradient pairs leave through a per-wave LDS tile as whole 128-byte lines (bf_tiles.h
-// store_pair_staged) instead of one 64-byte sector per lane: the forward kernel ran 0.255 ms without its stores and 0.553 with them.
-// Two workgroups per CU then have room for a 3-slot ring only (3 x 16 + 9.25 side + 18 staging = 75.25 KiB each), which by itself
-// costs 2-4 % (measured: 0.563 / 0.577 against 0.553 / 0.553 ms).
-#ifndef UCN_TRAIN_STAGED
-#define UCN_TRAIN_STAGED 1
-#endif
-#ifndef UCN_TRAIN_SLOTS
-#define UCN_TRAIN_SLOTS (UCN_TRAIN_OCC == 1 || UCN_TRAIN_WAVES == 8 ? 6 : (UCN_TRAIN_STAGED ? 3 : kTSlots))
-#endif
-#ifndef UCN_TRAIN_LEAD
-#define UCN_TRAIN_LEAD (UCN_TRAIN_OCC == 1 || UCN_TRAIN_WAVES == 8 ? 4 : (UCN_TRAIN_STAGED ? 1 : kTLead))
-#endif
-constexpr int kFtSlots = UCN_TRAIN_SLOTS, kFtLead = UCN_TRAIN_LEAD;
-// UCN_TRAIN_PIPE (r05): weight fragments requested kWAhead ahead of their MFMAs through a register pipe (bf_tiles.h tile_pair_pf)
-#ifndef UCN_TRAIN_PIPE
-#define UCN_TRAIN_PIPE 1
-#endif
-#ifndef UCN_TRAIN_PAIR_FWD
-#define UCN_TRAIN_PAIR_FWD 1
-#endif
-#ifndef UCN_TRAIN_PAIR_BWD
-#define UCN_TRAIN_PAIR_BWD 0
-#endif
-// Weight staging = the rendering engine's DMA ring (mlp_ring.h): a 64 KiB LDS ring of 4 x 16 KiB chunks filled by
-// global_load_lds two chunks ahead, one piece per four MFMAs, one barrier per chunk -- 64 KiB and <= 256 registers per
-// wave, so that TWO workgroups share a CU: at one wave per SIMD (the first version: two 64 KiB buffers, 456 registers)
+// Workgroup shape of the two training kernels: ONE 8-wave workgroup per CU whose waves share one ring (half the LDS-DMA weight stream
+// per sample of two 4-wave workgroups, still two waves per SIMD); the ring: 6 x 16 KiB, filled 4 chunks ahead.
+constexpr int kTrainWaves = 8;
+constexpr int kFtSlots = 6, kFtLead = 4;
+// Activation / gradient pairs leave through a per-wave LDS tile as whole 128-byte lines (bf_tiles.h store_pair_staged) instead of one
+// 64-byte sector per lane: the forward kernel ran 0.255 ms without its stores and 0.553 with them.
+// Weight fragments are requested kWAhead ahead of their MFMAs through a register pipe (bf_tiles.h tile_pair_pf).
+// Weight staging = the rendering engine's DMA ring (mlp_ring.h), filled by global_load_lds, one piece per four MFMAs, one barrier per
+// chunk, and <= 256 registers per wave: at one wave per SIMD (the first version: two 64 KiB buffers, 456 registers)
 // both kernels spent 75 % of their wave-cycles waiting (profiles/r02c/pmc_table_train.txt).
 constexpr int kFragsMax = 2 * 2 * 2 + 8 * 2 * 2 + 8 * 8 * 2 + 8 * 16 * 2 + 1 * 8 * 2;   // 440 with two feature tiles, 436 with one
 constexpr int kFragsPadded = (kFragsMax + kTChunk - 1) / kTChunk * kTChunk;               // 448: the stream is zero-padded
@@ -91,42 +62,25 @@ using TRing = Ring<kFragsPadded, kTChunk, kTrainWaves, kFtSlots, kFtLead>;      
 constexpr int kFwdFragsMax = 2 * 2 * 2 + 32 + 4 * 12 + 4 * 48;     // with the direction tile in the stream (inference): 276 / 280
 constexpr int kFwdPadded = (kFwdFragsMax + kTChunk - 1) / kTChunk * kTChunk;              // 288
 using FRing = Ring<kFwdPadded, kTChunk, kTrainWaves, kFtSlots, kFtLead>;
-template <int P, int NT_IN, int G0, int NG, class RING>
-__device__ __forceinline__ void tile_pair_sel(RING &ring, bf8 (&wp)[4], f32x16 (&acc)[P], const bf8 (&in)[NT_IN][2]) {
-    if constexpr (UCN_TRAIN_PIPE != 0) tile_pair_pf<P, NT_IN, G0, NG>(ring, wp, acc, in);
-    else tile_pair<P, NT_IN, G0>(ring, acc, in);
-}
-
-
-#ifndef UCN_TRAIN_FWD_WGS
-#define UCN_TRAIN_FWD_WGS UCN_TRAIN_OCC
-#endif
 // AUX (inference with rays-fastest lanes): the per-ray direction term is NOT pre-multiplied by the caller (pr0 / pr1 would
 // be 2 KiB per LANE there, 64 KiB of loads per wave); the ray's 32-column tile [dir_enc (27), 1, 0...] (a.ray_cols) enters
 // the two colour layers as one more input tile whose column 27 carries the layer bias, like in the rendering kernel.
 // The AUX form is inference only: its store paths fold away at compile time (88 -> 79 -> 70.5 ms per frame with them gone).
-// kInferWaves: workgroup shape of that form -- 4 = two 4-wave workgroups per CU like the training form; 8 / 12 = ONE
-// workgroup around a larger ring (the sky layer's bf16 shape; here 12 waves need 168 registers and spill: 72.6 ms, 8: 73.7).
-#ifndef UCN_INFER_WAVES
-#define UCN_INFER_WAVES 4
-#endif
-constexpr int kInferWaves = UCN_INFER_WAVES;
-using IRing = Ring<(kFwdFragsMax + 2 * kInferWaves - 1) / (2 * kInferWaves) * (2 * kInferWaves), kInferWaves == 4 ? kTChunk : 2 * kInferWaves,
-                   kInferWaves, kFtSlots, kFtLead>;
+// kInferWaves: workgroup shape of that form -- two 4-wave workgroups per CU (ONE workgroup of 8 / 12 waves around a larger ring, the
+// sky layer's bf16 shape, lost: 12 waves need 168 registers and spill: 72.6 ms, 8: 73.7).
+constexpr int kInferWaves = 4;
+using IRing = Ring<(kFwdFragsMax + 2 * kInferWaves - 1) / (2 * kInferWaves) * (2 * kInferWaves), kTChunk, kInferWaves, kFtSlots, kFtLead>;
 static_assert(IRing::kChunks * IRing::kChunk <= kFwdPadded, "the packed forward stream is padded to kFwdPadded fragments");
-template <bool AUX> struct FwdShape { using ring = FRing; static constexpr int waves = kTrainWaves, wgs = kTrainWaves == 8 ? 1 : UCN_TRAIN_FWD_WGS; };
-template <> struct FwdShape<true> { using ring = IRing; static constexpr int waves = kInferWaves, wgs = kInferWaves == 4 ? 2 : 1; };
+template <bool AUX> struct FwdShape { using ring = FRing; static constexpr int waves = kTrainWaves, wgs = 1; };
+template <> struct FwdShape<true> { using ring = IRing; static constexpr int waves = kInferWaves, wgs = 2; };
 
-// SIDE (r05, training form): the layer biases and the wave's two per-ray rows (pr0 / pr1: all 32 samples of a wave belong to one ray
+// SIDE (training form): the layer biases and the wave's two per-ray rows (pr0 / pr1: all 32 samples of a wave belong to one ray
 // when S % 32 == 0) are copied to LDS ONCE, before the chain, and every pair's accumulator start comes from there.  As global loads
 // inside the chain (r02-r04) each of the 12 pair starts carried a compiler-inserted `s_waitcnt vmcnt(0)` in front of its first MFMA
 // -- the compiler cannot see the hand-placed LDS-DMA stream, so its wait drained the whole weight look-ahead, twelve times per pass.
-#ifndef UCN_TRAIN_FWD_SIDE
-#define UCN_TRAIN_FWD_SIDE 1
-#endif
 constexpr int kSideBias = 16 + 64, kSideWave = 128;                    // float4: [bias_d0 (16) | bias_d1 (64)], then per wave [pr0 (64) | pr1 (64)]
 constexpr size_t kFwdSideBytes = (size_t)(kSideBias + kTrainWaves * kSideWave) * 16;
-constexpr size_t kStageBytes = UCN_TRAIN_STAGED ? kTrainWaves * kStageTile : 0;           // one staging tile per wave (training forms)
+constexpr size_t kStageBytes = kTrainWaves * kStageTile;           // one staging tile per wave (training forms)
 
 template <int NTF, bool AUX = false, bool SIDE = false>   // feature tiles: F <= 32 * NTF
 __global__ __launch_bounds__(64 * FwdShape<AUX>::waves, FwdShape<AUX>::wgs) void k_train_fwd(TrainFwdArgs aa) {
@@ -143,14 +97,12 @@ __global__ __launch_bounds__(64 * FwdShape<AUX>::waves, FwdShape<AUX>::wgs) void
     const uint32_t ray = a.level_dim ? bq % a.n_rays : bq / a.S;
     const uint32_t sample = a.level_dim ? ray * a.S + bq / a.n_rays : bq;   // position in the [ray][sample] outputs
     extern __shared__ __attribute__((aligned(16))) float s_w[];      // the weight ring [| side table] [| one staging tile per wave]
-    constexpr bool kStaged = UCN_TRAIN_STAGED != 0 && !AUX;
     const uint32_t wb0 = (blockIdx.x * (uint32_t)FwdShape<AUX>::waves + wave) * 32u;           // the wave's first sample
     const uint32_t n_rows = wb0 < a.M ? (a.M - wb0 < 32u ? a.M - wb0 : 32u) : 0u;
     uint8_t *stage = reinterpret_cast<uint8_t *>(s_w) + kFtSlots * kTChunk * 1024 + (SIDE ? kFwdSideBytes : 0) + wave * kStageTile;
     typename FwdShape<AUX>::ring ring(reinterpret_cast<const float *>(a.w), s_w, lane, wave);
     auto store_fwd = [&](uint16_t *dst, uint32_t ld, int tp, const bf8 (&t0)[2], const bf8 (&t1)[2]) {
-        if constexpr (kStaged) store_pair_staged(stage, dst, ld, wb0, n_rows, tp, lane, t0, t1);
-        else store_two<UCN_TRAIN_PAIR_FWD != 0>(dst, ld, sample, tp, h, t0, t1, live);
+        if constexpr (!AUX) store_pair_staged(stage, dst, ld, wb0, n_rows, tp, lane, t0, t1);      // (AUX: a.store == 0)
     };
     ring_start(ring);
     const float *side_b0 = nullptr, *side_b1 = nullptr, *side_p0 = nullptr, *side_p1 = nullptr;
@@ -200,19 +152,15 @@ __global__ __launch_bounds__(64 * FwdShape<AUX>::waves, FwdShape<AUX>::wgs) void
                 }
             }
             fin[ft][s] = pack8(v);
-#ifndef UCN_EXP_NOAUXSTORE
             if (a.fb && live && a.F % 8 == 0 && 32u * ft + 16u * s + 8u * h < a.F)
                 *reinterpret_cast<uint4 *>(a.fb + (size_t)sample * a.ld_fb + 32u * ft + 16u * s + 8u * h) = __builtin_bit_cast(uint4, fin[ft][s]);
-#endif
         }
-#ifndef UCN_EXP_NOAUXSTORE
     if (!AUX && a.ray_cols && live) {       // lane (j, h): columns 16 h .. 16 h + 15 of its sample's row
         const uint4 *src = reinterpret_cast<const uint4 *>(a.ray_cols + (size_t)ray * 32 + 16 * h);
         uint4 *dst = reinterpret_cast<uint4 *>(a.ray_dst + (size_t)sample * a.ld_act + 16 * h);
         dst[0] = src[0];
         dst[1] = src[1];
     }
-#endif
     ring.template boundary<0>();            // chunk 0 and the feature loads above land together
     // The bottleneck x = W_d1 h0 + b_d1 has NO activation behind it (models.py:508) and only linear maps consume it: the
     // colour layers take it COMPOSED, (W0x W_d1) h0 and (W1x W_d1) h0 (the host forms the two 256 x 64 products and folds
@@ -226,7 +174,7 @@ __global__ __launch_bounds__(64 * FwdShape<AUX>::waves, FwdShape<AUX>::wgs) void
     constexpr int G1 = 2 * NTF * 2, G2 = G1 + 32, G3 = G2 + 4 * P2;
     constexpr int NGF = G3 + 4 * (P3 + 4);                 // fragments this kernel consumes
     bf8 wp[kWSlots];                                             // fragment pipe
-    if constexpr (UCN_TRAIN_PIPE != 0) sfor<kWAhead>([&](auto g) { frag_fetch<g.value, NGF>(ring, wp); });
+    sfor<kWAhead>([&](auto g) { frag_fetch<g.value, NGF>(ring, wp); });
     // ---- density layer 0
     bf8 hin[10 + NA][2];                   // tiles 0..7: h1 (filled below), 8..9: h0, (10: the ray's direction tile)
     bf8 (&h0)[2][2] = reinterpret_cast<bf8(&)[2][2]>(hin[8]);
@@ -241,7 +189,7 @@ __global__ __launch_bounds__(64 * FwdShape<AUX>::waves, FwdShape<AUX>::wgs) void
         f32x16 a0[2];
         load_acc((SIDE ? side_b0 : a.bias_d0) + (0 * 2 + h) * 16, a0[0]);
         load_acc((SIDE ? side_b0 : a.bias_d0) + (1 * 2 + h) * 16, a0[1]);
-        tile_pair_sel<2, NTF, 0, NGF>(ring, wp, a0, fin);
+        tile_pair_pf<2, NTF, 0, NGF>(ring, wp, a0, fin);
 #pragma unroll
         for (int t = 0; t < 2; t++) {
             h0[t][0] = to_b(a0[t], 0, true);
@@ -257,7 +205,7 @@ __global__ __launch_bounds__(64 * FwdShape<AUX>::waves, FwdShape<AUX>::wgs) void
         f32x16 acc[2];
         load_acc((SIDE ? side_b1 : a.bias_d1) + ((2 * p) * 2 + h) * 16, acc[0]);
         load_acc((SIDE ? side_b1 : a.bias_d1) + ((2 * p + 1) * 2 + h) * 16, acc[1]);
-        tile_pair_sel<2, 2, G1 + 8 * p, NGF>(ring, wp, acc, h0);
+        tile_pair_pf<2, 2, G1 + 8 * p, NGF>(ring, wp, acc, h0);
         bf8 xp[2][2];
 #pragma unroll
         for (int o = 0; o < 2; o++) {
@@ -292,7 +240,7 @@ __global__ __launch_bounds__(64 * FwdShape<AUX>::waves, FwdShape<AUX>::wgs) void
                     load_acc(a.pr0 + ((size_t)ray * 8 + 2 * p + 1) * 32 + h * 16, acc[1]);
                 }
             }
-            tile_pair_sel<2, 2 + NA, G2 + P2 * p, NGF>(ring, wp, acc, reinterpret_cast<const bf8(&)[2 + NA][2]>(hin[8]));
+            tile_pair_pf<2, 2 + NA, G2 + P2 * p, NGF>(ring, wp, acc, reinterpret_cast<const bf8(&)[2 + NA][2]>(hin[8]));
 #pragma unroll
             for (int o = 0; o < 2; o++) {
                 hin[2 * p + o][0] = to_b(acc[o], 0, true);
@@ -322,7 +270,7 @@ __global__ __launch_bounds__(64 * FwdShape<AUX>::waves, FwdShape<AUX>::wgs) void
                     load_acc(a.pr1 + ((size_t)ray * 8 + 2 * p + 1) * 32 + h * 16, acc[1]);
                 }
             }
-            tile_pair_sel<2, 10 + NA, G3 + (P3 + 4) * p, NGF>(ring, wp, acc, hin);
+            tile_pair_pf<2, 10 + NA, G3 + (P3 + 4) * p, NGF>(ring, wp, acc, hin);
             bf8 hp[2][2];
 #pragma unroll
             for (int o = 0; o < 2; o++) {
@@ -333,7 +281,7 @@ __global__ __launch_bounds__(64 * FwdShape<AUX>::waves, FwdShape<AUX>::wgs) void
             mk[p] = mask16(acc[0]) | (mask16(acc[1]) << 16);
             f32x16 yo[1];                          // transient: four MFMAs, then only its three real rows are kept
             zero_acc(yo[0]);
-            tile_pair_sel<1, 2, G3 + (P3 + 4) * p + P3, NGF>(ring, wp, yo, hp);
+            tile_pair_pf<1, 2, G3 + (P3 + 4) * p + P3, NGF>(ring, wp, yo, hp);
             y3[0] += yo[0][0]; y3[1] += yo[0][1]; y3[2] += yo[0][2];
         });
         if (live && a.store) a.m2[(size_t)sample * 2 + h] = make_uint4(mk[0], mk[1], mk[2], mk[3]);
@@ -371,7 +319,7 @@ struct TrainBwdArgs {
 
 
 template <int NTF>
-__global__ __launch_bounds__(64 * kTrainWaves, kTrainWaves == 8 ? 1 : UCN_TRAIN_OCC) void k_train_bwd(TrainBwdArgs a) {
+__global__ __launch_bounds__(64 * kTrainWaves, 1) void k_train_bwd(TrainBwdArgs a) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int j = lane & 31, h = lane >> 5;
@@ -379,13 +327,11 @@ __global__ __launch_bounds__(64 * kTrainWaves, kTrainWaves == 8 ? 1 : UCN_TRAIN_
     const bool live = s0 < a.M;
     const uint32_t sample = live ? s0 : a.M - 1;
     extern __shared__ __attribute__((aligned(16))) float s_w[];      // the weight ring [| one staging tile per wave]
-    constexpr bool kStaged = UCN_TRAIN_STAGED != 0;
     const uint32_t wb0 = (blockIdx.x * (uint32_t)kTrainWaves + wave) * 32u;   // the wave's first sample
     const uint32_t n_rows = wb0 < a.M ? (a.M - wb0 < 32u ? a.M - wb0 : 32u) : 0u;
     uint8_t *stage = reinterpret_cast<uint8_t *>(s_w) + kFtSlots * kTChunk * 1024 + wave * kStageTile;
     auto store_bwd = [&](uint16_t *dst, uint32_t ld, int tp, const bf8 (&t0)[2], const bf8 (&t1)[2]) {
-        if constexpr (kStaged) store_pair_staged(stage, dst, ld, wb0, n_rows, tp, lane, t0, t1);
-        else store_two<UCN_TRAIN_PAIR_BWD != 0>(dst, ld, sample, tp, h, t0, t1, live);
+        store_pair_staged(stage, dst, ld, wb0, n_rows, tp, lane, t0, t1);
     };
     TRing ring(reinterpret_cast<const float *>(a.w), s_w, lane, wave);
     ring_start(ring);
@@ -431,7 +377,7 @@ __global__ __launch_bounds__(64 * kTrainWaves, kTrainWaves == 8 ? 1 : UCN_TRAIN_
     constexpr int H1 = 16, H2 = H1 + 128, H4 = H2 + 4 * 72;
     constexpr int NGF = H4 + 4 * NTF;                      // fragments this kernel consumes
     bf8 wp[kWSlots];                                             // fragment pipe
-    if constexpr (UCN_TRAIN_PIPE != 0) sfor<kWAhead>([&](auto g) { frag_fetch<g.value, NGF>(ring, wp); });
+    sfor<kWAhead>([&](auto g) { frag_fetch<g.value, NGF>(ring, wp); });
     bf8 din[16][2];                          // tiles 0..7: d1, 8..15: d0  (the order of [W1x^T | W0x^T])
     // ---- through the rgb layer and the second hidden layer's ReLU
     sfor<4>([&](auto pp) {
@@ -439,7 +385,7 @@ __global__ __launch_bounds__(64 * kTrainWaves, kTrainWaves == 8 ? 1 : UCN_TRAIN_
         f32x16 acc[2];
         zero_acc(acc[0]);
         zero_acc(acc[1]);
-        tile_pair_sel<2, 1, 4 * p, NGF>(ring, wp, acc, gin);
+        tile_pair_pf<2, 1, 4 * p, NGF>(ring, wp, acc, gin);
 #pragma unroll
         for (int o = 0; o < 2; o++) {
             const uint32_t bits = (m2w[p] >> (16 * o)) & 0xFFFFu;
@@ -454,7 +400,7 @@ __global__ __launch_bounds__(64 * kTrainWaves, kTrainWaves == 8 ? 1 : UCN_TRAIN_
         f32x16 acc[2];
         zero_acc(acc[0]);
         zero_acc(acc[1]);
-        tile_pair_sel<2, 8, H1 + 32 * p, NGF>(ring, wp, acc, reinterpret_cast<const bf8(&)[8][2]>(din[0]));
+        tile_pair_pf<2, 8, H1 + 32 * p, NGF>(ring, wp, acc, reinterpret_cast<const bf8(&)[8][2]>(din[0]));
 #pragma unroll
         for (int o = 0; o < 2; o++) {
             const uint32_t bits = (m1w[p] >> (16 * o)) & 0xFFFFu;
@@ -473,7 +419,7 @@ __global__ __launch_bounds__(64 * kTrainWaves, kTrainWaves == 8 ? 1 : UCN_TRAIN_
         f32x16 acc[2];
         zero_acc(acc[0]);
         zero_acc(acc[1]);
-        tile_pair_sel<2, 16, H2 + 72 * p, NGF>(ring, wp, acc, din);
+        tile_pair_pf<2, 16, H2 + 72 * p, NGF>(ring, wp, acc, din);
         if constexpr (p == 0) {
             if (a.graw && h == 0) {
                 const float gr = gr_head;
@@ -490,7 +436,7 @@ __global__ __launch_bounds__(64 * kTrainWaves, kTrainWaves == 8 ? 1 : UCN_TRAIN_
             gp[o][1] = to_b(acc[o], 1, false);
         }
         if (a.gx) store_bwd(a.gx, 256, 2 * p, gp[0], gp[1]);                  // (r04: gx = NULL -- the bottleneck's weight gradient is formed from d0^T h0, d1^T h0)
-        tile_pair_sel<2, 2, H2 + 72 * p + 64, NGF>(ring, wp, a0, gp);
+        tile_pair_pf<2, 2, H2 + 72 * p + 64, NGF>(ring, wp, a0, gp);
     });
     // ---- ReLU of h0
     bf8 gh0[2][2];
@@ -505,7 +451,7 @@ __global__ __launch_bounds__(64 * kTrainWaves, kTrainWaves == 8 ? 1 : UCN_TRAIN_
     f32x16 gf[NTF];
 #pragma unroll
     for (int ft = 0; ft < NTF; ft++) zero_acc(gf[ft]);
-    tile_pair_sel<NTF, 2, H4, NGF>(ring, wp, gf, gh0);
+    tile_pair_pf<NTF, 2, H4, NGF>(ring, wp, gf, gh0);
     if (live) {
 #pragma unroll
         for (int ft = 0; ft < NTF; ft++)
@@ -574,7 +520,7 @@ extern "C" int ucn_train_fwd(const float *feat, uint32_t F, const void *packed, 
         const size_t ilds = (size_t)IRing::kSlots * IRing::kChunk * 1024;
         if (F <= 32) hipLaunchKernelGGL((k_train_fwd<1, true>), igrid, iblock, ilds, (hipStream_t)stream, a);
         else hipLaunchKernelGGL((k_train_fwd<2, true>), igrid, iblock, ilds, (hipStream_t)stream, a);
-    } else if (UCN_TRAIN_FWD_SIDE && S % 32u == 0u && (((uintptr_t)bias_d0 | (uintptr_t)bias_d1 | (uintptr_t)pr0 | (uintptr_t)pr1) & 15u) == 0u) {
+    } else if (S % 32u == 0u && (((uintptr_t)bias_d0 | (uintptr_t)bias_d1 | (uintptr_t)pr0 | (uintptr_t)pr1) & 15u) == 0u) {
         // a wave's 32 samples are one ray's: biases + the wave's per-ray rows from an LDS side table (see k_train_fwd, SIDE)
         if (F <= 32) hipLaunchKernelGGL((k_train_fwd<1, false, true>), grid, dim3(64 * kTrainWaves), lds + kFwdSideBytes + kStageBytes, (hipStream_t)stream, a);
         else hipLaunchKernelGGL((k_train_fwd<2, false, true>), grid, dim3(64 * kTrainWaves), lds + kFwdSideBytes + kStageBytes, (hipStream_t)stream, a);

@@ -23,22 +23,15 @@
 namespace {
 
 __device__ __forceinline__ f32x16 mfma32x2(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-// the same instruction with the accumulator PINNED to the accumulation registers ("a" class): the 64-row shape of k_gemm_f32 holds 256
-// accumulator registers, exactly the AGPR half of the file -- left to the allocator they were split over both halves and ~1500
-// v_accvgpr_read / _write / _mov per chunk shuffled them around the MFMAs (r05 first build)
-__device__ __forceinline__ void mfma32x2_acc(float a, float b, f32x16 &c) {
-    asm volatile("v_mfma_f32_32x32x2_f32 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
-}
 __device__ __forceinline__ float f4e(const float4 &v, uint32_t s) { return s == 0 ? v.x : s == 1 ? v.y : s == 2 ? v.z : v.w; }
 
 // ---- k_gemm_f32: the weight streams through LDS in chunks of 4 CQ k (any N, K) ------------------------------------------------------
-// CQ = k quads per chunk (8: 32 k), OCC = workgroups per CU the register budget is cut for, RT = 32-row tiles per wave.
-//   <NT, 8, 2, 1>: 4 waves x 32 rows, two workgroups per CU (<= 256 registers): one workgroup's first-touch reads, stores and chunk
-//                  barriers sit behind the other one's MFMAs.
-//   <8, 8, 1, 2>:  4 waves x 64 rows x 256 columns, 256 accumulator registers, one workgroup per CU (the shape of the vendor library's
-//                  256 x 256 macro tile): every weight operand read from LDS and every staged weight quad feeds TWO MFMAs, a barrier
-//                  per 16 K MFMA cycles instead of 8 K.
-template <uint32_t NT, uint32_t CQ, uint32_t OCC, uint32_t RT>
+// CQ = k quads per chunk (8: 32 k), OCC = workgroups per CU the register budget is cut for.
+//   <NT, 8, 2>: 4 waves x 32 rows, two workgroups per CU (<= 256 registers): one workgroup's first-touch reads, stores and chunk
+//               barriers sit behind the other one's MFMAs.  (4 waves x 64 rows, one workgroup per CU -- the shape of the vendor library's
+//               256 x 256 macro tile -- MEASURED SLOWER: 80.8 / 99.6 TF at K = 256 / 544 against 93.9 / 120.5,
+//               profiles/r05/gemm_f32_variants.txt: with one wave per SIMD every LDS / barrier / first-touch bubble is exposed.)
+template <uint32_t NT, uint32_t CQ, uint32_t OCC>
 __global__ __launch_bounds__(256, OCC) void k_gemm_f32(const float *__restrict__ X, uint32_t ldx, const float *__restrict__ W, uint32_t ldw,
                                                        uint32_t K, GemmOut o) {
     constexpr uint32_t NC = NT * 32u, QS = NC + 1u;                // columns per pass; float4 stride between the k quads (+1: the
@@ -47,7 +40,8 @@ __global__ __launch_bounds__(256, OCC) void k_gemm_f32(const float *__restrict__
     constexpr uint32_t WPT = NC * CQ / 256u;                       // float4 of a weight chunk per thread
     constexpr uint32_t WPP = WPT >= 4u ? 4u : WPT, PARTS = WPT / WPP;    // staged through registers in pieces of <= 4 float4
     static_assert(PARTS * 2u <= NP || PARTS == 1u, "a piece is requested before one quad pair and written behind the next");
-    static_assert(RT == 1u || RT == 2u, "one or two 32-row tiles per wave");
+    constexpr uint32_t RT = 1u;                                    // 32-row tiles per wave (the statements below keep their two-tile shape:
+    //                                                                rewritten for one tile they compile to other instructions)
     extern __shared__ float4 s_w[];                                // [2 buffers][CQ quads][QS]
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u, i = lane & 31u, kk = lane >> 5;
     const uint32_t m0 = blockIdx.x * (128u * RT) + wave * (32u * RT), n0 = blockIdx.y * NC;
@@ -131,8 +125,7 @@ __global__ __launch_bounds__(256, OCC) void k_gemm_f32(const float *__restrict__
                 for (uint32_t t = 0; t < NT; t++) {
 #pragma unroll
                     for (uint32_t r = 0; r < RT; r++) {
-                        if constexpr (RT == 2u) mfma32x2_acc(f4e(b[t], s), f4e(a_cur[r][p], s), acc[r][t]);
-                        else acc[r][t] = mfma32x2(f4e(b[t], s), f4e(a_cur[r][p], s), acc[r][t]);
+                        acc[r][t] = mfma32x2(f4e(b[t], s), f4e(a_cur[r][p], s), acc[r][t]);
                     }
                     if (s == 3u && p + 1u < NP) {
                         b[t] = buf[(2u * (p + 1u) + kk) * QS + 32u * t + i];
@@ -151,21 +144,18 @@ __global__ __launch_bounds__(256, OCC) void k_gemm_f32(const float *__restrict__
     // Full tiles with 16-byte-aligned rows go through LDS (the weight buffers are free after the last barrier; a wave's staging tile is
     // 8.5 KiB, the launch reserves max(weight buffers, 4 such tiles)).
     // (the epilogue's bounds are made opaque HERE: its ~70 loop-invariant column / row predicates were hoisted above the chunk loop and
-    // held in scalar registers across it -- 210 of them spilled into vector lanes, which the 64-row shape does not have to spare)
+    // held in scalar registers across it -- 210 of them spilled into vector lanes)
     GemmOut oe = o;
     asm volatile("" : "+s"(oe.N), "+s"(oe.M), "+s"(oe.flags));
-    if constexpr (RT == 2u) asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");     // inline-asm MFMAs: their result latency (16 passes) is not known to the hazard recogniser
     const bool staged = NT >= 2u && (oe.flags & kGemmVec) && n0 + NC <= oe.N;
     float *tile = reinterpret_cast<float *>(s_w) + wave * kStageFloats;
     if constexpr (NT >= 2u) {
         if (staged) {
             gemm_store_staged<NT>(acc[0], oe, tile, m0, n0, lane);
-            if constexpr (RT == 2u) gemm_store_staged<NT>(acc[1], oe, tile, m0 + 32u, n0, lane);
             return;
         }
     }
     gemm_store_direct<NT>(acc[0], oe, m0 + i, n0, kk);
-    if constexpr (RT == 2u) gemm_store_direct<NT>(acc[1], oe, m0 + 32u + i, n0, kk);
 }
 
 // ---- k_gemm_f32_res: the WHOLE weight resident in LDS, persistent waves (r05) -------------------------------------------------------
@@ -408,12 +398,11 @@ extern "C" int ucn_gemm_f32_ex(const float *X, uint32_t ldx, const float *W, uin
     const uint32_t kq = ucn_div_up(K, 32) * 8u, nc = nt * 32u;
     const size_t res_lds = (size_t)kq * (nc + 1u) * 16u + (nt >= 2u ? 8u * kStageFloats * 4u : 0u);
     const uint32_t ntiles = ucn_div_up(M, 32);
-    static const bool no_res = getenv("UCN_GEMM_NO_RESIDENT") != nullptr;            // A/B switch (tools/gemm_f32_bench.py)
     int num_cus = 256;
     size_t max_lds = 0;
     gemm_device_limits(num_cus, max_lds);
     // (a device whose workgroups cannot hold the resident weight takes the weight-streaming kernel below)
-    if (N <= nc && res_lds <= 150u * 1024u && res_lds <= max_lds && ntiles >= 64u && !no_res) {
+    if (N <= nc && res_lds <= 150u * 1024u && res_lds <= max_lds && ntiles >= 64u) {
         const uint32_t wgs = ucn_div_up(ntiles, 8) < (uint32_t)num_cus ? ucn_div_up(ntiles, 8) : (uint32_t)num_cus;
 #define UCN_GR(NT) hipLaunchKernelGGL((k_gemm_f32_res<NT, 2u>), dim3(wgs), dim3(512), res_lds, st, X, ldx, W, ldw, K, o)
         switch (nt) {
@@ -426,22 +415,14 @@ extern "C" int ucn_gemm_f32_ex(const float *X, uint32_t ldx, const float *W, uin
         UCN_LAUNCH_CHECK("gemm_f32 (resident)");
         return 0;
     }
-    static const int variant = getenv("UCN_GEMM_VARIANT") ? atoi(getenv("UCN_GEMM_VARIANT")) : 0;       // A/B switch (tools/gemm_f32_bench.py)
-    // UCN_GEMM_VARIANT=2: 64-row waves, one workgroup per CU (the library's macro-tile shape).  MEASURED SLOWER (80.8 / 99.6 TF at
-    // K = 256 / 544 against 93.9 / 120.5 for two 32-row workgroups per CU, profiles/r05/gemm_f32_variants.txt): with one wave per SIMD
-    // every LDS / barrier / first-touch bubble is exposed, which the vendor kernel avoids by hand-scheduled assembly.  Kept as the A/B.
-    const uint32_t rt = (nt == 8u && variant == 2) ? 2u : 1u;
-    const dim3 grid(ucn_div_up(M, 128u * rt), ucn_div_up(N, nt * 32u));
+    const dim3 grid(ucn_div_up(M, 128u), ucn_div_up(N, nt * 32u));
 #define UCN_LDS(NT, CQ) (2u * CQ * (NT * 32u + 1u) * 16u > 4u * kStageFloats * 4u ? 2u * CQ * (NT * 32u + 1u) * 16u : 4u * kStageFloats * 4u)
-#define UCN_G(NT, CQ, OCC, RT) hipLaunchKernelGGL((k_gemm_f32<NT, CQ, OCC, RT>), grid, dim3(256), UCN_LDS(NT, CQ), st, X, ldx, W, ldw, K, o)
+#define UCN_G(NT, CQ, OCC) hipLaunchKernelGGL((k_gemm_f32<NT, CQ, OCC>), grid, dim3(256), UCN_LDS(NT, CQ), st, X, ldx, W, ldw, K, o)
     switch (nt) {
-        case 1: UCN_G(1, 8, 2, 1); break;
-        case 2: UCN_G(2, 8, 2, 1); break;
-        case 4: UCN_G(4, 8, 2, 1); break;
-        default:
-            if (rt == 2u) UCN_G(8, 8, 1, 2);
-            else UCN_G(8, 8, 2, 1);
-            break;
+        case 1: UCN_G(1, 8, 2); break;
+        case 2: UCN_G(2, 8, 2); break;
+        case 4: UCN_G(4, 8, 2); break;
+        default: UCN_G(8, 8, 2); break;
     }
 #undef UCN_G
 #undef UCN_LDS

@@ -37,12 +37,7 @@ typedef short s4v __attribute__((__vector_size__(4 * sizeof(short))));
 typedef uint32_t u4v __attribute__((ext_vector_type(4)));     // register-resident 16-byte units (arrays of HIP_vector_type structs
 typedef float f4v __attribute__((ext_vector_type(4)));        // behind lambda reference parameters were left in scratch memory)
 
-// (UCN_H3_EXP_*: timing-only experiment builds, tools/build_variant.sh -- results are garbage)
-#ifdef UCN_H3_EXP_NOMFMA
-__device__ __forceinline__ f32x16 mfma_h3(h8 a, h8 b, f32x16 c) { c[0] += (float)a[0] * (float)b[0]; return c; }
-#else
 __device__ __forceinline__ f32x16 mfma_h3(h8 a, h8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-#endif
 
 // e with amax 2^e in [2^14, 2^15): hi halves stay below f16's maximum (65504), lo halves of everything within 2^-15 of the maximum stay
 // normal.  Zero, infinite or NaN maxima: no scaling (e = 0); a subnormal maximum: 2^140.
@@ -195,7 +190,7 @@ constexpr uint32_t kH3Waves = 4u, kH3Threads = 64u * kH3Waves;     // 4 waves x 
 // vmcnt retires in issue order, so both streams have the same depth on purpose: a wait for a weight piece requested d steps ago also
 // waits for every activation piece requested before it.
 // Workgroup shape (r06, second build): 4 waves, two workgroups per CU (<= 256 registers each), instead of one 8-wave workgroup.  Per
-// workgroup of the 8-wave form, s_memtime (tools/h3_clock.py, N = K = 256): prologue 16 %, k loop 60 %, epilogue 17 %, maximum 7 % -- with
+// workgroup of the 8-wave form, s_memtime stamps (N = K = 256): prologue 16 %, k loop 60 %, epilogue 17 %, maximum 7 % -- with
 // one workgroup per CU nothing ran beside the 40 % that is not the loop.  Two independent workgroups put one's first-touch latency, its
 // 128 KiB of stores and its tail behind the other's MFMAs; the weight stream is fetched per 128 rows instead of per 256 (L2 -> LDS,
 // 13 B per clock and CU: nothing), its registers are the same (4 pieces per thread and step, two steps in flight).
@@ -210,31 +205,21 @@ constexpr uint32_t kH3PW = 2u;                                    // the weight 
 constexpr uint32_t h3_slot_units(uint32_t nt) { return nt * 128u < kH3Threads ? kH3Threads : nt * 128u; }     // 16-byte units per LDS slot
 constexpr size_t h3_lds_bytes(uint32_t nt) { return 2u * h3_slot_units(nt) * 16u + kH3Waves * kStageFloats * 4u; }   // weight ring + wave tiles
 
-#ifdef UCN_H3_CLOCK
-__device__ unsigned long long g_h3_clk[8];        // experiment build: summed s_memtime cycles per phase over the workgroups (thread 0)
-#define H3_STAMP(k) do { if (threadIdx.x == 0) { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); atomicAdd(&g_h3_clk[k], now_ - clk_last_); clk_last_ = now_; } } while (0)
-#else
-#define H3_STAMP(k) do { } while (0)
-#endif
-
 struct H3Scales {
     const float *xmax, *wmax;      // max |X|, max |W| (device): the operand scales
     uint32_t *ymax;                // atomic max of |Y| on the bit pattern (may be null)
-    uint32_t halves;               // 1: a workgroup owns all NT tiles of the packed stream.  2: the stream holds 2 NT tiles and workgroup
-    //                                b owns column half (b >> 3) & 1 of row tile (b >> 4) * 8 + (b & 7) -- the two halves of a row tile
-    //                                are 8 blocks apart: the same XCD (blocks go round robin over the 8 XCDs), dispatched back to back,
-    //                                so the second read of the activation rows is an L2 hit, not HBM traffic
+    uint32_t halves;               // always 1: a workgroup owns all NT tiles of the packed stream.  (2 was a lost route: two workgroups per
+    //                                row tile, each with one column half.  The host no longer offers it, but the kernel keeps the field and
+    //                                its selects: with them folded away k_gemm_h3<4, 8> compiled to a schedule that is 14 % SLOWER, 0.252
+    //                                against 0.221 ms at N = K = 128, M = 2^20, profiles/knob_cleanup/bench_ab.txt.)
 };
 
 // KS > 0: the k loop fully unrolled for K = 16 KS exactly (the layer widths of this model: 64, 128, 256).  Not a nicety: across a loop's
 // back edge hipcc's wait-count pass does not carry the ORDER of the loads in flight -- a register requested in the previous trip is
 // waited for as if every load of that trip had to land first (vmcnt(6) where 14 were allowed: the requests' real depth fell from four
 // steps to one and a half).  In straight-line code its counts are exact.  KS = 0: the loop, any K.
-#ifndef UCN_H3_OCC_NARROW
-#define UCN_H3_OCC_NARROW 2          // experiment: workgroups per CU asked for the NT <= 4 instantiations (3: <= 168 registers)
-#endif
 template <uint32_t NT, uint32_t KS>
-__global__ __launch_bounds__(kH3Threads, NT <= 4u ? UCN_H3_OCC_NARROW : 2) void k_gemm_h3(const float *__restrict__ X, uint32_t ldx, const u4v *__restrict__ Wp, uint32_t K_rt,
+__global__ __launch_bounds__(kH3Threads, 2) void k_gemm_h3(const float *__restrict__ X, uint32_t ldx, const u4v *__restrict__ Wp, uint32_t K_rt,
                                                           uint32_t ksteps_rt, H3Scales sc, GemmOut o) {
     constexpr uint32_t PX = kH3PX, PW = kH3PW;
     static_assert(PX % PW == 0u, "the weight sets rotate inside a chunk");
@@ -249,10 +234,7 @@ __global__ __launch_bounds__(kH3Threads, NT <= 4u ? UCN_H3_OCC_NARROW : 2) void 
     const uint32_t half = sc.halves == 2u ? (blockIdx.x >> 3) & 1u : 0u;
     const uint32_t rtile = sc.halves == 2u ? (blockIdx.x >> 4) * 8u + (blockIdx.x & 7u) : blockIdx.x;
     const uint32_t m0 = rtile * (32u * kH3Waves) + wave * 32u, n0 = half * (NT * 32u);
-    if (rtile * (32u * kH3Waves) >= o.M) return;                   // (halves == 2: the grid is rounded up to whole groups of 16 blocks)
-#ifdef UCN_H3_CLOCK
-    unsigned long long clk_last_ = __builtin_amdgcn_s_memtime();
-#endif
+    if (rtile * (32u * kH3Waves) >= o.M) return;
     float *tile = reinterpret_cast<float *>(s_ring + 2u * SLOT) + wave * kStageFloats;
     const int ex = h3_exponent(*sc.xmax), ew = h3_exponent(*sc.wmax);
     const float neg1 = h3_neg1();
@@ -300,12 +282,9 @@ __global__ __launch_bounds__(kH3Threads, NT <= 4u ? UCN_H3_OCC_NARROW : 2) void 
         // 1. requests: at a chunk's first step the NEXT chunk of activations (its registers were parked in LDS at the end of the
         //    previous step), then the weight piece PX steps ahead into the set stored one step ago.  Past the end: the loop form
         //    re-reads the first chunk / step (unused), the unrolled form drops the requests.
-#ifndef UCN_H3_EXP_NOW
         if (KS == 0u || s + PW < KS) load_w(s + PW, wreg[P % PW]);       // (before the chunk: the wait for it at the end of step s + 1
-#endif                                                               //  must not also wait for the chunk)
-#ifndef UCN_H3_EXP_NOX
+        //                                                                   must not also wait for the chunk)
         if (P == 0u && (KS == 0u || s + PX < KS)) load_chunk(s / PX + 1u);
-#endif
         // 2. this step's activations from the wave tile: zero past K, scale, split
         const float *xr = tile + i * RS + 16u * P + 8u * g;
         const f4v x0 = *reinterpret_cast<const f4v *>(xr), x1 = *reinterpret_cast<const f4v *>(xr + 4u);
@@ -350,9 +329,7 @@ __global__ __launch_bounds__(kH3Threads, NT <= 4u ? UCN_H3_OCC_NARROW : 2) void 
         //    at a chunk's last step the next chunk of activations over this one (wave-private: the wave's LDS operations stay in order)
         if (KS == 0u || s + 1u < KS) store_w(s + 1u, wreg[(P + 1u) % PW]);
         if (P == PX - 1u && (KS == 0u || s + 1u < KS)) store_chunk();
-#ifndef UCN_H3_EXP_NOBAR
         __syncthreads();
-#endif
     };
     // prologue: W(0) and the first chunk go to LDS at once; W(1 .. PX - 1) fill the register sets
     load_w(0u, wreg[0]);
@@ -362,7 +339,6 @@ __global__ __launch_bounds__(kH3Threads, NT <= 4u ? UCN_H3_OCC_NARROW : 2) void 
     store_w(0u, wreg[0]);
     store_chunk();
     __syncthreads();
-    H3_STAMP(0);
     if constexpr (KS > 0u) {
         static_assert(KS % PX == 0u, "whole chunks");
         h3_static_for<KS>([&](auto sc_) { step(std::integral_constant<uint32_t, decltype(sc_)::value % PX>{}, decltype(sc_)::value); });
@@ -371,7 +347,6 @@ __global__ __launch_bounds__(kH3Threads, NT <= 4u ? UCN_H3_OCC_NARROW : 2) void 
             h3_static_for<PX>([&](auto pc) { step(pc, s + decltype(pc)::value); });
         }
     }
-    H3_STAMP(1);
     // undo the operand scales (exact), then the shared epilogue through the wave tile
 #pragma unroll
     for (uint32_t t = 0; t < NT; t++)
@@ -381,9 +356,6 @@ __global__ __launch_bounds__(kH3Threads, NT <= 4u ? UCN_H3_OCC_NARROW : 2) void 
     asm volatile("" : "+s"(oe.N), "+s"(oe.M), "+s"(oe.flags));      // (see k_gemm_f32: keeps the epilogue's predicates out of the loop's registers)
     float mx = 0.0f;                                                // always tracked (a run-time choice would put it in scratch memory)
     bool done = false;
-#ifdef UCN_H3_EXP_NOSTORE
-    if (acc[0][0] != 123.456f) return;
-#endif
     if constexpr (NT >= 2u) {
         if ((oe.flags & kGemmVec) && n0 + NT * 32u <= oe.N) {
             // the epilogue's optional pieces are template flags of the store (run-time tests inside it cost the exact engine's resident
@@ -405,12 +377,10 @@ __global__ __launch_bounds__(kH3Threads, NT <= 4u ? UCN_H3_OCC_NARROW : 2) void 
         }
     }
     if (!done) mx = gemm_store_direct<NT, true>(acc, oe, m0 + i, n0, g);
-    H3_STAMP(2);
     if (sc.ymax) {                                                  // uniform
         __syncthreads();                                            // every wave is done with its tile: the weight ring is scratch now
         block_amax_to_slot(mx, reinterpret_cast<float *>(s_ring), sc.ymax);
     }
-    H3_STAMP(3);
 }
 
 // ---- k_wgrad_h3 ----------------------------------------------------------------------------------------------------------------------
@@ -587,14 +557,6 @@ extern "C" int ucn_amax_f32(const float *X, uint32_t ldx, uint64_t M, uint32_t K
     return 0;
 }
 
-#ifdef UCN_H3_CLOCK
-extern "C" int ucn_h3_clock_read(unsigned long long *out8, int reset) {
-    if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_h3_clk), 8 * sizeof(unsigned long long)) != hipSuccess) return 1;
-    if (reset) { unsigned long long z[8] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_h3_clk), z, sizeof(z)) != hipSuccess) return 1; }
-    return 0;
-}
-#endif
-
 extern "C" uint64_t ucn_relu_bits_words(uint64_t M, uint32_t N) { return gemm_bits_words(M, N); }
 
 extern "C" uint64_t ucn_pack_h3_bytes(uint32_t N, uint32_t K) { return (uint64_t)h3_ksteps(K) * h3_tiles(N) * 2048u; }
@@ -647,17 +609,12 @@ extern "C" int ucn_gemm_h3_x2(const float *X, uint32_t ldx, const void *packed, 
     o.bits_out = reinterpret_cast<uint32_t *>(relu_bits_out);
     o.bits_in = reinterpret_cast<const uint32_t *>(mask_bits);
     const uint32_t ks = h3_ksteps(K);
-    // UCN_H3_HALVES=2 (experiment, measured SLOWER: 0.755 against 0.656 ms at N = K = 256, profiles/r06/gemm_h3_notes.txt): 256-wide outputs as
-    // two workgroups of 4 tiles per row tile instead of one of 8 -- the 4-tile kernel moves 4.3 TB/s on its own 128-wide shape, but here the
-    // activation rows are fetched twice and the second fetch is not the L2 hit the block pairing was meant to make it
-    static const bool two_wg = getenv("UCN_H3_HALVES") != nullptr && atoi(getenv("UCN_H3_HALVES")) == 2;
-    const uint32_t halves = (h3_tiles(N) == 8u && two_wg) ? 2u : 1u;
-    H3Scales sc{xmax, wmax, reinterpret_cast<uint32_t *>(ymax), halves};
-    const uint32_t rtiles = ucn_div_up(M, 32u * kH3Waves);
-    const dim3 grid(halves == 2u ? ucn_div_up(rtiles, 8) * 16u : rtiles);
+    // (256-wide outputs as two workgroups of 4 tiles per row tile instead of one of 8 measured SLOWER: 0.755 against 0.656 ms at N = K = 256,
+    // profiles/r06/gemm_h3_notes.txt -- the activation rows are fetched twice and the second fetch is no L2 hit)
+    H3Scales sc{xmax, wmax, reinterpret_cast<uint32_t *>(ymax), 1u};
+    const dim3 grid(ucn_div_up(M, 32u * kH3Waves));
     hipStream_t st = (hipStream_t)stream;
-    static const bool no_unroll = getenv("UCN_H3_NO_UNROLL") != nullptr;              // A/B switch: every shape through the loop form
-    const uint32_t ku = (K % 16u == 0u && !no_unroll) ? K / 16u : 0u;                 // unrolled forms: K = 64 (wide outputs only), 128, 256
+    const uint32_t ku = K % 16u == 0u ? K / 16u : 0u;                 // unrolled forms: K = 64 (wide outputs only), 128, 256
 #define UCN_H3K(NT, KS) hipLaunchKernelGGL((k_gemm_h3<NT, KS>), grid, dim3(kH3Threads), h3_lds_bytes(NT), st, X, ldx, reinterpret_cast<const u4v *>(packed), K, ks, sc, o)
 #define UCN_H3(NT)                                         \
     do {                                                   \
@@ -666,7 +623,7 @@ extern "C" int ucn_gemm_h3_x2(const float *X, uint32_t ldx, const void *packed, 
         else if (ku == 4u) UCN_H3K(NT, 4);                 \
         else UCN_H3K(NT, 0);                               \
     } while (0)
-    switch (h3_tiles(N) / halves) {
+    switch (h3_tiles(N)) {
         case 1: UCN_H3(1); break;
         case 2: UCN_H3(2); break;
         case 4: UCN_H3(4); break;

@@ -32,30 +32,10 @@ namespace {
 //     is invisible after the cast back to float.
 // (The first version ran one THREAD per ray with its arrays in scratch memory: 6.4 ms per 2.46 M rays; the stores
 //  are now coalesced across the lanes of the ray's wave as well.)
-#ifdef UCN_WAVE_SHFL          // the first form: butterflies / Hillis-Steele steps over __shfl (ds_bpermute_b32)
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_scan_d(double v, int lane) {      // inclusive
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const double u = __shfl_up(v, o, 64);
-        if (lane >= o) v += u;
-    }
-    return v;
-}
-__device__ __forceinline__ float wave_max_f(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-#else
+// wave reductions / scans: DPP forms (wave_dpp.h)
 __device__ __forceinline__ double wave_sum_d(double v) { return wave_sum_dpp<double>(v); }
 __device__ __forceinline__ double wave_scan_d(double v, int) { return wave_scan_dpp<double>(v); }      // inclusive
 __device__ __forceinline__ float wave_max_f(float v) { return wave_max_dpp(v); }
-#endif
 // #{j < len : f(j) <= x} / #{j < len : f(j) < x} for a non-decreasing f
 template <bool STRICT, class F>
 __device__ __forceinline__ uint32_t count_before(F f, uint32_t len, float x) {
@@ -286,36 +266,10 @@ __global__ __launch_bounds__(256) void k_cone_basis(const float *__restrict__ ca
 }
 
 // ------------------------------------------------------------------ composite
-#ifdef UCN_WAVE_SHFL
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-// inclusive prefix sum across the 64 lanes
-__device__ __forceinline__ float wave_scan(float v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const float u = __shfl_up(v, o, 64);
-        if (lane >= o) v += u;
-    }
-    return v;
-}
-__device__ __forceinline__ float wave_excl(float incl, int lane) {      // inclusive -> exclusive (0 in lane 0)
-    const float u = __shfl_up(incl, 1, 64);
-    return lane == 0 ? 0.0f : u;
-}
-__device__ __forceinline__ uint32_t wave_count(uint32_t cnt) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-    return cnt;
-}
-#else
 __device__ __forceinline__ float wave_sum(float v) { return wave_sum_dpp<float>(v); }
 __device__ __forceinline__ float wave_scan(float v, int) { return wave_scan_dpp<float>(v); }            // inclusive
 __device__ __forceinline__ float wave_excl(float incl, int) { return wave_shift_up1<float>(incl); }    // -> exclusive
 __device__ __forceinline__ uint32_t wave_count(uint32_t cnt) { return wave_sum_dpp<uint32_t>(cnt); }
-#endif
 __device__ __forceinline__ float nan_to_num_inf(float v) {
     // torch.nan_to_num(x, nan=inf): NaN -> +inf (as given), +inf -> FLT_MAX, -inf -> -FLT_MAX
     if (v != v) return INFINITY;

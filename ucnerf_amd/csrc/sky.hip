@@ -46,11 +46,8 @@ constexpr int kBL[7] = {0, 128, 256, 384, 512, 656, 784};
 constexpr int kBV = 912, kBEnd = kBV + 72;                                // 984
 // workgroup = kBWaves waves sharing one ring of kBSlots chunks of kBChunk fragments; 12 waves = three per SIMD from ONE
 // workgroup (96 KiB ring + 14 KiB side table; two 4-wave workgroups with a 64 KiB ring each: 2 per SIMD)
-#ifndef UCN_SKY_BF_WAVES
-#define UCN_SKY_BF_WAVES 12
-#endif
-constexpr int kBWaves = UCN_SKY_BF_WAVES, kBChunk = kBWaves == 4 ? 16 : 2 * kBWaves, kBSlots = 4, kBLead = 2;
-constexpr int kBPadded = (kBEnd + kBChunk - 1) / kBChunk * kBChunk;      // 984 (24-fragment chunks) / 992 (16)
+constexpr int kBWaves = 12, kBChunk = 2 * kBWaves, kBSlots = 4, kBLead = 2;
+constexpr int kBPadded = (kBEnd + kBChunk - 1) / kBChunk * kBChunk;      // 984 (24-fragment chunks)
 using BRing = Ring<kBPadded, kBChunk, kBWaves, kBSlots, kBLead>;
 constexpr uint64_t kOffBf = kOffMv + 128 * 288;
 constexpr uint64_t kOffExp = kOffBf + (uint64_t)kBPadded * 256;          // 9 layer exponents (ints) + report, 32 slots
@@ -231,7 +228,7 @@ __device__ __forceinline__ bf8 (&pick_b(bf8 (&a)[9][2], bf8 (&b)[9][2]))[9][2] {
     else return b;
 }
 
-__global__ __launch_bounds__(64 * kBWaves, kBWaves == 4 ? 2 : 1) void k_sky_mlp_bf(SkyArgs a) {
+__global__ __launch_bounds__(64 * kBWaves, 1) void k_sky_mlp_bf(SkyArgs a) {
     extern __shared__ __attribute__((aligned(16))) float s_w[];   // weight ring + side table
     const float *side = s_w + kBSlots * kBChunk * 256;
     const int lane = threadIdx.x & 63;
@@ -536,10 +533,7 @@ extern "C" int ucn_sky_pack(const ucn_sky_t *s, ucn_stream_t stream) {
     float *sc = s->packed + kOffScaled;
     SkyPtrs ptrs;
     for (int i = 0; i < 8; i++) { ptrs.w[i] = s->w_pts[i]; ptrs.b[i] = s->b_pts[i]; }
-    // UCN_SKY_NO_SCALES=1 (tests / experiments): every exponent 0, i.e. round 2's unscaled operands
-    static const bool no_scales = getenv("UCN_SKY_NO_SCALES") && atoi(getenv("UCN_SKY_NO_SCALES")) != 0;
-    if (no_scales) hipLaunchKernelGGL(k_fill_zero, dim3(1), dim3(256), 0, st, reinterpret_cast<float *>(exps), 16u);
-    else hipLaunchKernelGGL(k_sky_scales, dim3(1), dim3(256), 0, st, s->w_pts[0], s->b_pts[0], ptrs, M5, Mv, exps);
+    hipLaunchKernelGGL(k_sky_scales, dim3(1), dim3(256), 0, st, s->w_pts[0], s->b_pts[0], ptrs, M5, Mv, exps);
     auto scaled = [&](const float *src, uint32_t n, uint32_t cols, uint32_t split, int ia, int ib, float *dst) {
         hipLaunchKernelGGL(k_sky_scaled_copy, dim3(ucn_div_up(n, 256)), dim3(256), 0, st, src, n, cols, split, ia, ib, exps, dst);
         return (const float *)dst;

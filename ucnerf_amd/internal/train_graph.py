@@ -393,21 +393,15 @@ def _colour_forward(h0, A0, pr0, W1h, A1, pr1, Wr, br, S):
     # r05: the per-ray terms are the GEMMs' row-group bias, the ReLUs their epilogue, and the rgb row (models.py:663) sits inside the
     # node so that its d X GEMM can carry h2's ReLU derivative as a mask epilogue (r04: ucn_bias_relu / ucn_relu_backward_reduce passes)
     pr0, pr1 = pr0.contiguous(), pr1.contiguous()
-    if os.environ.get("UCN_COLOUR_CAT", "1") != "0":
-        # r06: layer 1's two products as ONE over the concatenated input [h1 | h0] (K = 256 + 64): h1 is written straight into its
-        # column block of the buffer; the second, accumulating pass re-read the whole [M, 256] output (0.65 + 0.69 ms -> 0.82 + a
-        # 0.1 ms copy).  UCN_COLOUR_CAT=0: the two-pass form (A/B)
-        M = h0.shape[0]
-        cat = torch.empty(M, W1h.shape[1] + h0.shape[1] + dense_f32.ACT_PAD, device=h0.device, dtype=torch.float32)[:, :W1h.shape[1] + h0.shape[1]]
-        cat[:, W1h.shape[1]:] = h0      # (before the kernel writes h1 into its view: an in-place torch op bumps the shared version
-        h1 = G(h0, A0, None, dense_f32.RELU, out=cat[:, :W1h.shape[1]], rowbias=pr0, rgroup=S)  # counter and h1's records would go stale)
-        dense_f32.tag_amax_of_parts(cat, h1, h0)
-        h2 = G(cat, torch.cat([W1h, A1], dim=1), None, dense_f32.RELU, out=dense_f32.rows_buffer(M, W1h.shape[0], h0.device), rowbias=pr1, rgroup=S)
-        del cat
-    else:
-        h1 = G(h0, A0, None, dense_f32.RELU, rowbias=pr0, rgroup=S)
-        h2 = G(h1, W1h)
-        G(h0, A1, None, dense_f32.ACCUMULATE | dense_f32.RELU, out=h2, rowbias=pr1, rgroup=S)
+    # layer 1's two products as ONE over the concatenated input [h1 | h0] (K = 256 + 64): h1 is written straight into its column block
+    # of the buffer; a second, accumulating pass re-read the whole [M, 256] output (0.65 + 0.69 ms -> 0.82 + a 0.1 ms copy)
+    M = h0.shape[0]
+    cat = torch.empty(M, W1h.shape[1] + h0.shape[1], device=h0.device, dtype=torch.float32)
+    cat[:, W1h.shape[1]:] = h0      # (before the kernel writes h1 into its view: an in-place torch op bumps the shared version
+    h1 = G(h0, A0, None, dense_f32.RELU, out=cat[:, :W1h.shape[1]], rowbias=pr0, rgroup=S)  # counter and h1's records would go stale)
+    dense_f32.tag_amax_of_parts(cat, h1, h0)
+    h2 = G(cat, torch.cat([W1h, A1], dim=1), None, dense_f32.RELU, out=dense_f32.rows_buffer(M, W1h.shape[0], h0.device), rowbias=pr1, rgroup=S)
+    del cat
     rgbl = G(h2, Wr, br.float().contiguous())
     return h1, h2, rgbl
 
