@@ -177,6 +177,7 @@ def test_composite_backward_matches_oracle_autograd(S, opaque):
     alpha_weights / composite (render.py:155-216) on the host: weights, rgb, depth, acc and the gradients of a loss
     that uses all four (so every branch of the backward -- direct weight gradient, colour, background, acc, depth,
     the 300-sentinel below acc 0.6 -- is exercised)."""
+    from ucnerf_amd.internal.march_level import Fenceposts
     from ucnerf_amd.internal.train_graph import _Composite
     g = torch.Generator().manual_seed(S + int(opaque))
     N = 300
@@ -200,7 +201,8 @@ def test_composite_backward_matches_oracle_autograd(S, opaque):
     loss_of(w, out["rgb"], out["depth"], out["acc"]).backward()
 
     d1, r1 = density.cuda().requires_grad_(True), rgbs.cuda().requires_grad_(True)
-    w1, rgb1, dep1, acc1 = _Composite.apply(d1, r1, sdist.cuda(), near.cuda(), far.cuda(), dirs.cuda().contiguous(), bg, opaque)
+    posts = Fenceposts(sdist.cuda(), near.cuda(), far.cuda(), None, None)
+    w1, rgb1, dep1, acc1 = _Composite.apply(d1, r1, posts, dirs.cuda().contiguous(), bg, opaque)
     (w1 * cw.cuda()).sum().add((rgb1 * cr.cuda()).sum()).add((dep1 * cd.cuda()).sum() * 0.1).add((acc1 * ca.cuda()).sum()).backward()
     assert float((w1.cpu() - w).abs().max()) <= 2e-6
     assert float((rgb1.cpu() - out["rgb"]).abs().max()) <= 5e-6
@@ -803,25 +805,24 @@ def test_half_table_gather_equals_the_fp32_gather_of_the_rounded_table():
     """Under autocast the training forward gathers a HALF copy of the tables, as the reference's _grid_encode does
     (gridencoder/grid.py:41-44).  The kernel converts each row to fp32 and interpolates in fp32, so its features are
     bit-identical to the fp32-table kernel run on the table rounded to half -- every level type (dense, hashed, pairs)."""
-    from ucnerf_amd.internal import train_graph as tg
+    from ucnerf_amd.internal import march_level as ml, train_graph as tg
     spec = rm.make_spec("tiny")
     model, _ = hip_model_for(spec, rm.init_state(spec, seed=41))
     model.train()
     N = 300
-    rays = H.to_dev(rm.synthetic_rays(N, seed=42))
+    rays = ml.Rays(H.to_dev(rm.synthetic_rays(N, seed=42)), 2)
     g = torch.Generator(device="cuda").manual_seed(43)
     for mlp, S in ((model.prop_mlp_0, 64), (model.nerf_mlp, 128)):
         sdist = torch.sort(torch.rand(N, S + 1, device="cuda", generator=g), dim=-1).values.contiguous()
         basis = torch.nn.functional.normalize(torch.randn(N, 2, 3, device="cuda", generator=g), dim=-1).reshape(N, 6).contiguous()
         flip, spin = torch.rand(N, S, device="cuda", generator=g), torch.rand(N, S, device="cuda", generator=g)
-        f32 = lambda k: rays[k].reshape(N, -1).float().contiguous()
-        geom = (sdist, f32("near"), f32("far"), f32("origins"), f32("directions"), basis, f32("radii"), flip, spin)
+        posts = ml.Fenceposts(sdist, rays.near, rays.far, None, basis)
         emb = mlp.encoder.embeddings
         with torch.no_grad():
-            half, c16, _ = tg._FieldFeatures.apply(emb, mlp, geom, N, S, 0.5, 0, True)
+            half, c16, _ = tg._FieldFeatures.apply(emb, mlp, posts, rays, flip, spin, S, 0.5, 0, True)
             keep = emb.data.clone()
             emb.data.copy_(keep.half().float())
-            full, c32, _ = tg._FieldFeatures.apply(emb, mlp, geom, N, S, 0.5, 0, False)
+            full, c32, _ = tg._FieldFeatures.apply(emb, mlp, posts, rays, flip, spin, S, 0.5, 0, False)
             emb.data.copy_(keep)
         assert torch.equal(half, full) and torch.equal(c16, c32)
         assert float(half.abs().max()) > 0

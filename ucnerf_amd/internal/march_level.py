@@ -1,0 +1,178 @@
+"""What a sampling level needs around its kernels, once for both marches (ref models.py:97-324): `Model._march` (models.py, the
+fused inference march) and `march_train` (train_graph.py, the autograd march) walk the same level schedule.  Here: the batch's
+rays, the level plan and anneal value, the random draws in the reference's order, a level's fenceposts with the choice between
+an entry point and its `_tdist` sibling, and the result dictionaries.  What runs in between -- featurisation, dense layers,
+compositing, the sky and brightness tails -- stays with each march (kernels in one, autograd nodes in the other)."""
+import functools
+
+import numpy as np
+import torch
+
+from .. import _lib
+
+
+def _f32(t, n, c):
+    t = t.reshape(n, c)
+    if t.dtype != torch.float32:
+        t = t.float()
+    return t.contiguous()
+
+
+class Rays:
+    """The batch as float32 [N, c] tensors, its leading shape `prefix`, and the optional keys that pin the random draws: `rand_vec`
+    [N, 3 * num_levels] and `noise` (batch['march_noise']: per level a dict of 'jitter', 'flip', 'spin'; {} where nothing is pinned)."""
+    __slots__ = ("o", "d", "vd", "cam", "rad", "near", "far", "prefix", "N", "dev", "rand_vec", "noise")
+
+    def __init__(self, batch, num_levels, on_device=True):
+        origins = batch['origins']
+        if on_device:
+            _lib.require_device(origins, "batch['origins']")
+        self.dev, self.prefix = origins.device, tuple(origins.shape[:-1])
+        self.N = N = int(np.prod(self.prefix))
+        self.o, self.d, self.vd, self.cam = (_f32(batch[k], N, 3) for k in ('origins', 'directions', 'viewdirs', 'cam_dirs'))
+        self.rad, self.near, self.far = (_f32(batch[k], N, 1) for k in ('radii', 'near', 'far'))
+        rand_vec, noise = batch.get('rand_vec'), batch.get('march_noise')
+        self.rand_vec = None if rand_vec is None else _f32(rand_vec, N, 3 * num_levels)
+        self.noise = [{}] * num_levels if noise is None else noise
+
+
+def anneal_of(anneal_slope, train_frac):
+    """models.py:179-184: Schlick's bias of the training fraction; 1 with the slope off."""
+    return (anneal_slope * train_frac) / ((anneal_slope - 1) * train_frac + 1) if anneal_slope > 0 else 1.
+
+
+def level_plan(model):
+    """[(i_level, is_prop, S, mlp, dilation)] of models.py:152-168.  dilation = bias + multiplier / (the product of the earlier
+    levels' sample counts); 0.0 with use_dilation off (both knobs <= 0), which ucn_resample reads as "resample undilated"."""
+    use_dilation = model.dilation_bias > 0 or model.dilation_multiplier > 0
+    plan, prod_num_samples = [], 1
+    for i_level in range(model.num_levels):
+        is_prop = i_level < model.num_levels - 1
+        S = model.num_prop_samples if is_prop else model.num_nerf_samples
+        mlp = model.get_submodule(f'prop_mlp_{i_level}') if is_prop else model.nerf_mlp
+        dilation = model.dilation_bias + model.dilation_multiplier * 1.0 / prod_num_samples if use_dilation else 0.0
+        if use_dilation and not dilation > 0:
+            # (a negative dilation_bias) the reference would dilate by it; ucn_resample takes dilation <= 0 as the UNdilated branch
+            raise NotImplementedError(f"dilation {dilation} <= 0 at level {i_level} with use_dilation on: not the shipped configuration")
+        prod_num_samples *= S
+        plan.append((i_level, is_prop, S, mlp, dilation))
+    return plan
+
+
+def draws(rays, i_level, S, rand, single_jitter):
+    """(jitter, flip, spin, rvec) of one level, in the reference's order: stepfun.py:216 rand(N, 1 | S), render.py:123 and :124
+    rand(N, S) each -- these three only with `rand`, else None -- then render.py:140 randn(N, 3) always.  A value the batch pins
+    is taken instead of drawn (and consumes nothing of the generator); the others are still drawn, in that order."""
+    N, dev = rays.N, rays.dev
+    jitter = flip = spin = None
+    if rand:
+        pn = rays.noise[i_level]
+        jcols = 1 if single_jitter else S
+        jitter = _f32(pn['jitter'], N, jcols) if 'jitter' in pn else torch.rand(N, jcols, device=dev)
+        flip = _f32(pn['flip'], N, S) if 'flip' in pn else torch.rand(N, S, device=dev)
+        spin = _f32(pn['spin'], N, S) if 'spin' in pn else torch.rand(N, S, device=dev)
+    rvec = torch.randn(N, 3, device=dev) if rays.rand_vec is None else rays.rand_vec[:, 3 * i_level:3 * i_level + 3].contiguous()
+    return jitter, flip, spin, rvec
+
+
+@functools.lru_cache(maxsize=None)
+def _u_table(num_samples, train, device):
+    """stepfun.py:203-216: (the u grid of the inverse-CDF lookup on `device`, max_jitter); constant per S, so cached."""
+    eps = float(torch.finfo(torch.float32).eps)
+    if train:
+        u_max = eps + (1 - eps) / num_samples
+        max_jitter = (1 - u_max) / (num_samples - 1) - eps
+        u = torch.linspace(0, 1 - u_max, num_samples)
+    else:
+        pad = 1 / (2 * num_samples)
+        max_jitter = 0.0
+        u = torch.linspace(pad, 1. - pad - eps, num_samples)
+    return u.to(device), max_jitter
+
+
+def s_to_t(model, sdist, near, far, stream):
+    """models.py:208 `tdist = s_to_t(sdist)` on the device (ucn_s_to_t) for a model with a warped ray-distance curve; None for
+    the identity curve, whose kernels derive t from sdist, near and far themselves (nothing extra is launched)."""
+    if not model._raydist_curve:
+        return None
+    N, S1 = sdist.shape
+    tdist = torch.empty(N, S1, device=sdist.device)
+    _lib.check(_lib.load().ucn_s_to_t(sdist.data_ptr(), near.data_ptr(), far.data_ptr(), N, S1, model._raydist_curve,
+                                      float(model.power_lambda), tdist.data_ptr(), stream))
+    return tdist
+
+
+class Fenceposts:
+    """A level's fenceposts: sdist [N, S+1] with the batch's near / far, their metric form tdist for a warped Model.raydist_fn, and the
+    cone basis [N, 6].  The one place that knows which sibling of an entry point reads them, with which pointer arguments."""
+    __slots__ = ("sdist", "near", "far", "tdist", "basis")
+
+    def __init__(self, sdist, near, far, tdist, basis):
+        self.sdist, self.near, self.far, self.tdist, self.basis = sdist, near, far, tdist, basis
+
+    def entry(self, lib, name):
+        """lib.<name> (ucn_march_features[_backward], ucn_composite[_backward]), or its `_tdist` sibling on metric fenceposts."""
+        return getattr(lib, name if self.tdist is None else name + '_tdist')
+
+    def geometry(self, rays, flip, spin, sl=slice(None)):
+        """The featurisation's geometry arguments for the rays `sl`: what the kernels derive t from, then the cones."""
+        fence = (self.sdist, self.near, self.far) if self.tdist is None else (self.tdist,)
+        return [t[sl].data_ptr() for t in fence + (rays.o, rays.d, self.basis, rays.rad)] + [
+            None if flip is None else flip[sl].data_ptr(), None if spin is None else spin[sl].data_ptr()]
+
+    def compositing(self, sl=slice(None), backward=False):
+        """The compositing arguments for the rays `sl`; the forward `_tdist` sibling also reads the batch's metric far."""
+        fence = (self.sdist, self.near, self.far) if self.tdist is None else (self.tdist,) if backward else (self.tdist, self.far)
+        return [t[sl].data_ptr() for t in fence]
+
+
+def fenceposts(model, rays, i_level, S, dilation, train_frac, rand, prev, weights_prev, stream, pinned_sdist=None):
+    """The level's draws, then ucn_resample from the previous level's fenceposts `prev` and weights (None at level 0), ucn_cone_basis
+    and s_to_t: (Fenceposts, flip, spin).  pinned_sdist: the training route's test hook -- fenceposts handed in instead of the
+    resampling kernel's (no gradient flows through them in the reference either, stepfun.py:251-294)."""
+    lib, N, dev = _lib.load(), rays.N, rays.dev
+    jitter, flip, spin, rvec = draws(rays, i_level, S, rand, model.single_jitter)
+    u_tab, max_jitter = _u_table(S, bool(rand), dev)
+    sdist = torch.empty(N, S + 1, device=dev)
+    basis = torch.empty(N, 6, device=dev)
+    sdist_prev, n_prev = (None, 0) if prev is None else (prev.sdist, prev.sdist.shape[1] - 1)
+    wp = None if weights_prev is None else weights_prev.detach().contiguous()
+    _lib.check(lib.ucn_resample(_lib.ptr(sdist_prev), _lib.ptr(wp), n_prev, dilation, anneal_of(model.anneal_slope, train_frac),
+                                float(model.resample_padding), u_tab.data_ptr(), _lib.ptr(jitter),
+                                0 if jitter is None else jitter.shape[1], max_jitter, N, S, sdist.data_ptr(), stream))
+    if pinned_sdist is not None:
+        sdist = _f32(pinned_sdist, N, S + 1).clone()
+    _lib.check(lib.ucn_cone_basis(rays.cam.data_ptr(), rvec.data_ptr(), N, basis.data_ptr(), stream))
+    return Fenceposts(sdist, rays.near, rays.far, s_to_t(model, sdist, rays.near, rays.far, stream), basis), flip, spin
+
+
+# ---- result dictionaries (the keys of ref models.py:262-324) -------------------------------------------------------------
+def rendering_entry(rgb, depth, acc, weights, extras, prefix, sdist=None, rgbs=None, n_vis=16):
+    """rgb [N, 3], depth [N], acc [N], weights [N, S]; with extras [N, 4] (compute_extras: distance mean, 5 %, median, 95 %) also the
+    'ray_*' keys: the first n_vis rays' fenceposts, weights and colours (rgbs None, a proposal level: zeros until `broadcast_final`)."""
+    N, S = weights.shape
+    r = dict(rgb=rgb.reshape(prefix + (3,)), depth=depth.reshape(prefix), acc=acc.reshape(prefix))
+    if extras is not None:
+        for j, k in enumerate(('distance_mean', 'distance_percentile_5', 'distance_median', 'distance_percentile_95')):
+            r[k] = extras[:, j].reshape(prefix)
+    r['weights'] = weights.reshape(prefix + (S,))
+    if extras is not None:
+        r['ray_sdist'], r['ray_weights'] = sdist[:n_vis], weights[:n_vis]
+        r['ray_rgbs'] = rgbs[:n_vis] if rgbs is not None else torch.zeros(min(n_vis, N), S, 3, device=weights.device)
+    return r
+
+
+def broadcast_final(renderings):
+    """ref models.py:313-324: the last level's composited ray colours stand in for the proposal levels' ray_rgbs."""
+    final = (renderings[-1]['ray_rgbs'] * renderings[-1]['ray_weights'][..., None]).sum(dim=-2)
+    for r in renderings[:-1]:
+        r['ray_rgbs'] = final[:, None, :].expand(r['ray_rgbs'].shape)
+
+
+def history_entry(coord, density, rgbs, sdist, weights, prefix):
+    """coord [N, S, 3], density [N, S], rgbs [N, S, 3] or None (zeros), sdist [N, S+1], weights [N, S]."""
+    N, S = weights.shape
+    rgb = torch.zeros(N, S, 3, device=weights.device) if rgbs is None else rgbs
+    return dict(coord=coord.reshape(prefix + (S, 3)), density=density.reshape(prefix + (S,)), rgb=rgb.reshape(prefix + (S, 3)),
+                raw_grad_density=None, grad_pred=None, normals=None, normals_pred=None, roughness=None,
+                sdist=sdist.reshape(prefix + (S + 1,)).clone(), weights=weights.reshape(prefix + (S,)).clone())

@@ -24,7 +24,9 @@ import torch.nn as nn
 
 from .. import _lib
 from ..gridencoder import GridEncoder
+from . import march_level as ml
 from .extrinsic_optimizer import BrightnessCorrection
+from .march_level import _f32, _u_table  # noqa: F401  (_u_table: not used here, kept importable for tests and tools)
 from .sky import NeRF, render_rays  # noqa: F401  (names kept importable like upstream)
 
 
@@ -53,13 +55,6 @@ def set_kwargs(self, kwargs):
         setattr(self, k, v)
 
 
-def _f32(t, n, c):
-    t = t.reshape(n, c)
-    if t.dtype != torch.float32:
-        t = t.float()
-    return t.contiguous()
-
-
 def glo_fold(W0, b0, W1, b1, a, b):
     """The colour layers (lin_second_stage_0 over [bottleneck, dir_enc], lin_second_stage_1 over [h1, bottleneck, dir_enc])
     with a modulation x' = x * a + b of the bottleneck that is the SAME for every ray (a, b [NB]) folded into their weights:
@@ -72,9 +67,6 @@ def glo_fold(W0, b0, W1, b1, a, b):
     W0f[:, :NB] = W0x * a
     W1f[:, NW:NW + NB] = W1x * a
     return W0f, b0 + W0x @ b, W1f, b1 + W1x @ b
-
-
-_U_CACHE = {}
 
 
 # Model.raydist_fn -> the curve id of include/ucnerf_march.h (UCN_RAYDIST_*).  coord.py:151-172 selects a callable by its
@@ -106,38 +98,6 @@ def raydist_curve(fn):
     raise ValueError(f"Model.raydist_fn={fn!r}: only the reference's curves are supported (None, 'piecewise', "
                      f"'power_transformation', torch.{', torch.'.join(RAYDIST_TORCH)}); the HIP kernels evaluate each "
                      "curve and its inverse themselves (csrc/raydist.h)")
-
-
-def s_to_t(model, sdist, near, far, stream):
-    """models.py:208 `tdist = s_to_t(sdist)` on the device (ucn_s_to_t) for a model with a warped ray-distance curve; None for
-    the identity curve, whose kernels derive t from sdist, near and far themselves (nothing extra is launched)."""
-    curve = model._raydist_curve
-    if not curve:
-        return None
-    N, S1 = sdist.shape
-    tdist = torch.empty(N, S1, device=sdist.device)
-    _lib.check(_lib.load().ucn_s_to_t(sdist.data_ptr(), near.data_ptr(), far.data_ptr(), N, S1, curve,
-                                      float(model.power_lambda), tdist.data_ptr(), stream))
-    return tdist
-
-
-def _u_table(num_samples, train, device):
-    """stepfun.py:203-216: the u grid of the inverse-CDF lookup (constant per S)."""
-    key = (num_samples, bool(train), str(device))
-    hit = _U_CACHE.get(key)
-    if hit is None:
-        eps = float(torch.finfo(torch.float32).eps)
-        if train:
-            u_max = eps + (1 - eps) / num_samples
-            max_jitter = (1 - u_max) / (num_samples - 1) - eps
-            u = torch.linspace(0, 1 - u_max, num_samples)
-        else:
-            pad = 1 / (2 * num_samples)
-            max_jitter = 0.0
-            u = torch.linspace(pad, 1. - pad - eps, num_samples)
-        hit = (u.to(device), max_jitter)
-        _U_CACHE[key] = hit
-    return hit
 
 
 class MLP(nn.Module):
@@ -631,47 +591,72 @@ class Model(nn.Module):
         cache[id(mlp)] = (key, out)
         return out
 
+    def _mlp_route(self, *, mlp, is_prop, S, desc, mixed, rays, posts, dirb, co, compact, density, rgbs, weights, main, nc):
+        """The level's dense layers as one callable run(fb, sl, r0, n): density (and colours) of the n rays `sl` = [r0, r0 + n) from the
+        feature buffer `fb`.  Chosen once per level: mixed-precision proposal / NeRF level, compacted colour pass, plain ucn_field_mlp."""
+        lib, st, dev = _lib.load(), _lib.stream(), rays.dev
+        L, C = mlp.encoder.num_levels, mlp.encoder.level_dim
+        dir_row = dirb.numel() // max(rays.N, 1)            # (an empty batch runs no pass)
+        rf = int(bool(self.rays_fastest))
+        if mixed is not None and is_prop:
+            w0, b0_, w1, b1_ = mixed['prop']
+            def run(fb, sl, r0, n):
+                _lib.check(lib.ucn_prop_train_fwd(fb.data_ptr(), L * C, w0.shape[0], w0.data_ptr(), b0_.data_ptr(), w1.data_ptr(),
+                                                  b1_.data_ptr(), float(mlp.density_bias), 1, n * S, density[sl].data_ptr(), n, C, st))
+        elif mixed is not None:
+            # the ray's direction tile rides in the weight stream's last input tile (no per-ray terms to pre-multiply)
+            vd_enc = mixed['enc'](rays.vd)
+            feat_flags = C | (_lib.FEAT_BF16 if mixed['feat_flag'] else 0)
+            def run(fb, sl, r0, n):
+                _lib.check(lib.ucn_train_fwd(fb.data_ptr(), L * C, mixed['packed'].data_ptr(), mixed['bias0'].data_ptr(),
+                                             mixed['bias1'].data_ptr(), mixed['biasr'].data_ptr(), None, None, n, S,
+                                             None, None, None, None, 0, vd_enc[sl].data_ptr(), None, None, mixed['head'],
+                                             density[sl].data_ptr(), rgbs[sl].data_ptr(), None, None, None, feat_flags, st))
+        elif compact:
+            composite = posts.entry(lib, 'ucn_composite')
+            bg, opaque = float(self.bg_intensity_range[0]), int(bool(self.opaque_background))
+            def run(fb, sl, r0, n):
+                # density head -> weights of this pass's rays -> alive list -> colour layers of the alive samples
+                _lib.check(lib.ucn_field_mlp(ctypes.byref(desc), fb.data_ptr(), n * S, S, rf, None, density[sl].data_ptr(),
+                                             None, None, st))
+                _lib.check(composite(density[sl].data_ptr(), None, *posts.compositing(sl), rays.d[sl].data_ptr(), bg, opaque,
+                                     n, S, weights[sl].data_ptr(), main[sl].data_ptr(), None, st))
+                if getattr(self, '_alive_idx', None) is None or self._alive_idx.numel() < n * S or self._alive_idx.device != dev:
+                    self._alive_idx = torch.empty(max(n, nc) * S, dtype=torch.int32, device=dev)
+                    self._alive_cnt = torch.zeros(1, dtype=torch.int32, device=dev)
+                _lib.check(lib.ucn_compact_alive(weights[sl].data_ptr(), n, S, rf, float(self.compact_min_weight),
+                                                 self._alive_idx.data_ptr(), self._alive_cnt.data_ptr(), st))
+                rgbs[sl].zero_()
+                _lib.check(lib.ucn_field_rgb_compacted(ctypes.byref(desc), fb.data_ptr(), n * S, S, rf,
+                                                       dirb[r0 * dir_row:].data_ptr(), self._alive_idx.data_ptr(),
+                                                       self._alive_cnt.data_ptr(), rgbs[sl].data_ptr(), st))
+                stats = getattr(self, '_alive_stats', None)
+                if stats is not None:                              # diagnostics (tools/alive_fraction.py): forces a sync
+                    stats.append((int(self._alive_cnt.item()), n * S))
+        else:
+            def run(fb, sl, r0, n):
+                _lib.check(lib.ucn_field_mlp(
+                    ctypes.byref(desc), fb.data_ptr(), n * S, S, rf | co,
+                    None if is_prop else dirb[r0 * dir_row:].data_ptr(),
+                    density[sl].data_ptr(), None if is_prop else rgbs[sl].data_ptr(), None, st))
+        return run
+
     def _march(self, rand, batch, train_frac, compute_extras, eval_camidx, want_history):
         lib = _lib.load()
-        origins = batch['origins']
-        _lib.require_device(origins, "batch['origins']")
-        dev = origins.device
-        prefix = tuple(origins.shape[:-1])
-        N = int(np.prod(prefix))
-        o = _f32(origins, N, 3)
-        d = _f32(batch['directions'], N, 3)
-        vd = _f32(batch['viewdirs'], N, 3)
-        cam = _f32(batch['cam_dirs'], N, 3)
-        rad = _f32(batch['radii'], N, 1)
-        near = _f32(batch['near'], N, 1)
-        far = _f32(batch['far'], N, 1)
-        pinned_vec = batch.get('rand_vec')
-        if pinned_vec is not None:
-            pinned_vec = _f32(pinned_vec, N, 3 * self.num_levels)
-        pinned = batch.get('march_noise')
+        rays = ml.Rays(batch, self.num_levels)
+        N, dev, prefix = rays.N, rays.dev, rays.prefix
         st = _lib.stream()
         cfg = self.config
-        n_vis = getattr(cfg, 'vis_num_rays', 16)
-
-        if self.anneal_slope > 0:
-            anneal = (self.anneal_slope * train_frac) / ((self.anneal_slope - 1) * train_frac + 1)
-        else:
-            anneal = 1.
         self.last_march_route = 'fused'       # diagnostics / tests: the route of the last forward (train_graph: 'train_graph')
         nerf_desc = self.nerf_mlp.field(glo_fold=True)          # a GLO field: zero codes folded into the colour layers
         dirb = torch.empty(lib.ucn_field_dir_floats(ctypes.byref(nerf_desc), N), device=dev)
-        _lib.check(lib.ucn_field_dir_bias(ctypes.byref(nerf_desc), vd.data_ptr(), N, dirb.data_ptr(), st))
+        _lib.check(lib.ucn_field_dir_bias(ctypes.byref(nerf_desc), rays.vd.data_ptr(), N, dirb.data_ptr(), st))
 
         renderings, ray_history = [], []
-        sdist_prev = weights_prev = None
-        n_prev = 0
-        prod_num_samples = 1
+        posts = weights = None
         nerf_chunk = max(1, int(self.max_chunk_rays))
         nerf_row = self.num_nerf_samples * self.nerf_mlp.encoder.num_levels * self.nerf_mlp.encoder.level_dim
-        for i_level in range(self.num_levels):
-            is_prop = i_level < self.num_levels - 1
-            S = self.num_prop_samples if is_prop else self.num_nerf_samples
-            mlp = self.get_submodule(f'prop_mlp_{i_level}') if is_prop else self.nerf_mlp
+        for i_level, is_prop, S, mlp, dilation in ml.level_plan(self):
             desc = mlp.field(glo_fold=not is_prop)
             L, C = mlp.encoder.num_levels, mlp.encoder.level_dim
             # max_chunk_rays is quoted for the NeRF level; a proposal level (fewer samples, narrower features) takes
@@ -679,59 +664,31 @@ class Model(nn.Module):
             chunk = nerf_chunk
             if is_prop and S * L * C < nerf_row:
                 chunk = max(nerf_chunk, min(nerf_chunk * nerf_row // (S * L * C) // 256 * 256, 1 << 16))
-            dilation = self.dilation_bias + self.dilation_multiplier * 1.0 / prod_num_samples
-            if not (self.dilation_bias > 0 or self.dilation_multiplier > 0):
-                dilation = 0.0                                           # ref :167 use_dilation False: resample undilated
-            elif not dilation > 0:
-                # use_dilation is on but the value is not positive (a negative dilation_bias): the reference would run
-                # max_dilate_weights with it; ucn_resample reads dilation <= 0 as the UNdilated branch -- refuse
-                raise NotImplementedError(f"dilation {dilation} <= 0 with use_dilation on: outside the shipped configuration")
-            prod_num_samples *= S
-            # ---- random draws, in the reference's order (stepfun.py:216, render.py:123,124,140)
-            jitter = flip = spin = None
-            u_tab, max_jitter = _u_table(S, bool(rand), dev)
-            if rand:
-                pn = pinned[i_level] if pinned is not None else {}
-                jcols = 1 if self.single_jitter else S
-                jitter = _f32(pn['jitter'], N, jcols) if 'jitter' in pn else torch.rand(N, jcols, device=dev)
-                flip = _f32(pn['flip'], N, S) if 'flip' in pn else torch.rand(N, S, device=dev)
-                spin = _f32(pn['spin'], N, S) if 'spin' in pn else torch.rand(N, S, device=dev)
-            if pinned_vec is not None:
-                rvec = pinned_vec[:, 3 * i_level:3 * i_level + 3].contiguous()
-            else:
-                rvec = torch.randn(N, 3, device=dev)
+            # ---- random draws and fenceposts (resample -> cone basis -> metric fenceposts of a warped raydist_fn)
+            posts, flip, spin = ml.fenceposts(self, rays, i_level, S, dilation, train_frac, rand, posts, weights, st)
+            march_features = posts.entry(lib, 'ucn_march_features')
             # ---- outputs of the level
-            sdist = torch.empty(N, S + 1, device=dev)
             density = torch.empty(N, S, device=dev)
             rgbs = None if is_prop else torch.empty(N, S, 3, device=dev)
             weights = torch.empty(N, S, device=dev)
             main = torch.empty(N, 5, device=dev)
             extras = torch.empty(N, 4, device=dev) if compute_extras else None
             coord = torch.empty(N, S, 3, device=dev) if want_history else None
-            basis = torch.empty(N, 6, device=dev)
             nc = min(chunk, N)
             feat = torch.empty(L * nc * S * C, device=dev)
             mixed = self._mixed_level(mlp, is_prop, L * C)
             self._mixed_levels = getattr(self, '_mixed_levels', 0) + (mixed is not None)      # diagnostics / tests
-            if mixed is not None and not is_prop:
-                vd_enc = mixed['enc'](vd)
-            _lib.check(lib.ucn_resample(_lib.ptr(sdist_prev), _lib.ptr(weights_prev), n_prev, dilation, anneal,
-                                        float(self.resample_padding), u_tab.data_ptr(), _lib.ptr(jitter),
-                                        0 if jitter is None else jitter.shape[1], max_jitter, N, S,
-                                        sdist.data_ptr(), st))
-            _lib.check(lib.ucn_cone_basis(cam.data_ptr(), rvec.data_ptr(), N, basis.data_ptr(), st))
-            # a warped raydist_fn: the level's metric fenceposts once (models.py:208), read by the tdist siblings below
-            tdist = s_to_t(self, sdist, near, far, st)
-            march_features = lib.ucn_march_features if tdist is None else lib.ucn_march_features_tdist
-            composite = lib.ucn_composite if tdist is None else lib.ucn_composite_tdist
-            fence = (sdist, near, far) if tdist is None else (tdist,)          # geometry: what the kernels derive t from
-            fence_c = (sdist, near, far) if tdist is None else (tdist, far)    # compositing: + the batch's metric far
             prof = getattr(self, '_prof', None)
             prof_every = max(1, int(getattr(self, '_prof_every', 1)))
             # Two HIP streams: featurisation of pass i+1 (L2-request / VALU bound) runs beside the MLP of pass i
             # (MFMA bound) on a second feature buffer; the hardware splits the CUs between the two kernels.
             overlap = bool(self.overlap_streams) and N > chunk
             co = _lib.LAUNCH_CORESIDENT if (overlap and not is_prop and self.overlap_streams != 2) else 0     # launch shapes that share a CU (2: plain shapes, tails only)
+            compact = (not is_prop) and (not want_history) and self.compact_min_weight > 0 and mlp.mlp_mode == 1 and mixed is None
+            run_mlp = self._mlp_route(mlp=mlp, is_prop=is_prop, S=S, desc=desc, mixed=mixed, rays=rays, posts=posts, dirb=dirb, co=co,
+                                      compact=compact, density=density, rgbs=rgbs, weights=weights, main=main, nc=nc)
+            feat_desc = ctypes.byref(desc if mixed is None else mixed['desc'])
+            feat_layout = ((2 if self.rays_fastest else 0) | co) if mixed is None else (2 | mixed['table_flag'] | (mixed['feat_flag'] if not is_prop else 0))
             cur = torch.cuda.current_stream()
             feats = [feat]
             if overlap:
@@ -757,11 +714,7 @@ class Model(nn.Module):
                 if timed:
                     e0.record(fstream)
                 _lib.check(march_features(
-                    ctypes.byref(desc if mixed is None else mixed['desc']), *[t[sl].data_ptr() for t in fence],
-                    o[sl].data_ptr(), d[sl].data_ptr(), basis[sl].data_ptr(), rad[sl].data_ptr(),
-                    None if flip is None else flip[sl].data_ptr(), None if spin is None else spin[sl].data_ptr(),
-                    float(self.std_scale), n, S, int(self.levels_per_block),
-                    ((2 if self.rays_fastest else 0) | co) if mixed is None else (2 | mixed['table_flag'] | (mixed['feat_flag'] if not is_prop else 0)),
+                    feat_desc, *posts.geometry(rays, flip, spin, sl), float(self.std_scale), n, S, int(self.levels_per_block), feat_layout,
                     fb.data_ptr(), None if coord is None else coord[sl].data_ptr(), None, fstream.cuda_stream))
                 if timed:
                     e1.record(fstream)
@@ -771,44 +724,7 @@ class Model(nn.Module):
                     cur.wait_event(ready)
                 if timed and overlap:
                     m0.record(cur)
-                compact = (not is_prop) and (not want_history) and self.compact_min_weight > 0 and mlp.mlp_mode == 1 and mixed is None
-                if mixed is not None and is_prop:
-                    w0, b0_, w1, b1_ = mixed['prop']
-                    _lib.check(lib.ucn_prop_train_fwd(fb.data_ptr(), L * C, w0.shape[0], w0.data_ptr(), b0_.data_ptr(), w1.data_ptr(),
-                                                      b1_.data_ptr(), float(mlp.density_bias), 1, n * S, density[sl].data_ptr(), n, C, st))
-                elif mixed is not None:
-                    # the ray's direction tile rides in the weight stream's last input tile (no per-ray terms to pre-multiply)
-                    _lib.check(lib.ucn_train_fwd(fb.data_ptr(), L * C, mixed['packed'].data_ptr(), mixed['bias0'].data_ptr(),
-                                                 mixed['bias1'].data_ptr(), mixed['biasr'].data_ptr(), None, None, n, S,
-                                                 None, None, None, None, 0, vd_enc[sl].data_ptr(), None, None, mixed['head'],
-                                                 density[sl].data_ptr(), rgbs[sl].data_ptr(), None, None, None,
-                                                 C | (_lib.FEAT_BF16 if mixed['feat_flag'] else 0), st))
-                elif compact:
-                    # density head -> weights of this pass's rays -> alive list -> colour layers of the alive samples
-                    rf = int(bool(self.rays_fastest))
-                    _lib.check(lib.ucn_field_mlp(ctypes.byref(desc), fb.data_ptr(), n * S, S, rf, None, density[sl].data_ptr(),
-                                                 None, None, st))
-                    _lib.check(composite(density[sl].data_ptr(), None, *[t[sl].data_ptr() for t in fence_c],
-                                         d[sl].data_ptr(), float(self.bg_intensity_range[0]),
-                                         int(bool(self.opaque_background)), n, S, weights[sl].data_ptr(), main[sl].data_ptr(),
-                                         None, st))
-                    if getattr(self, '_alive_idx', None) is None or self._alive_idx.numel() < n * S or self._alive_idx.device != dev:
-                        self._alive_idx = torch.empty(max(n, nc) * S, dtype=torch.int32, device=dev)
-                        self._alive_cnt = torch.zeros(1, dtype=torch.int32, device=dev)
-                    _lib.check(lib.ucn_compact_alive(weights[sl].data_ptr(), n, S, rf, float(self.compact_min_weight),
-                                                     self._alive_idx.data_ptr(), self._alive_cnt.data_ptr(), st))
-                    rgbs[sl].zero_()
-                    _lib.check(lib.ucn_field_rgb_compacted(ctypes.byref(desc), fb.data_ptr(), n * S, S, rf,
-                                                           dirb[r0 * (dirb.numel() // N):].data_ptr(), self._alive_idx.data_ptr(),
-                                                           self._alive_cnt.data_ptr(), rgbs[sl].data_ptr(), st))
-                    stats = getattr(self, '_alive_stats', None)
-                    if stats is not None:                              # diagnostics (tools/alive_fraction.py): forces a sync
-                        stats.append((int(self._alive_cnt.item()), n * S))
-                else:
-                    _lib.check(lib.ucn_field_mlp(
-                        ctypes.byref(desc), fb.data_ptr(), n * S, S, int(bool(self.rays_fastest)) | co,
-                        None if is_prop else dirb[r0 * (dirb.numel() // N):].data_ptr(),
-                        density[sl].data_ptr(), None if is_prop else rgbs[sl].data_ptr(), None, st))
+                run_mlp(fb, sl, r0, n)
                 if overlap:
                     mlp_done[i_pass % 2] = torch.cuda.Event()
                     mlp_done[i_pass % 2].record(cur)
@@ -817,39 +733,18 @@ class Model(nn.Module):
                     prof.append((i_level, n, e0, e1, m0, e2))      # features: e0..e1 on its stream, MLP: m0..e2
             if overlap:
                 cur.wait_stream(side)
-            _lib.check(composite(density.data_ptr(), _lib.ptr(rgbs), *[t.data_ptr() for t in fence_c],
-                                 d.data_ptr(), float(self.bg_intensity_range[0]),
-                                 int(bool(self.opaque_background)), N, S, weights.data_ptr(),
-                                 main.data_ptr(), _lib.ptr(extras), st))
-            rendering = dict(rgb=main[:, 0:3].reshape(prefix + (3,)), depth=main[:, 3].reshape(prefix),
-                             acc=main[:, 4].reshape(prefix))
-            if compute_extras:
-                rendering['distance_mean'] = extras[:, 0].reshape(prefix)
-                rendering['distance_percentile_5'] = extras[:, 1].reshape(prefix)
-                rendering['distance_median'] = extras[:, 2].reshape(prefix)
-                rendering['distance_percentile_95'] = extras[:, 3].reshape(prefix)
-            rendering['weights'] = weights.reshape(prefix + (S,))
-            level_rgb = rgbs if rgbs is not None else None
-            if compute_extras:
-                rendering['ray_sdist'] = sdist[:n_vis]
-                rendering['ray_weights'] = weights[:n_vis]
-                rendering['ray_rgbs'] = (level_rgb[:n_vis] if level_rgb is not None
-                                         else torch.zeros(min(n_vis, N), S, 3, device=dev))
-            renderings.append(rendering)
+            _lib.check(posts.entry(lib, 'ucn_composite')(
+                density.data_ptr(), _lib.ptr(rgbs), *posts.compositing(), rays.d.data_ptr(),
+                float(self.bg_intensity_range[0]), int(bool(self.opaque_background)), N, S, weights.data_ptr(),
+                main.data_ptr(), _lib.ptr(extras), st))
+            renderings.append(ml.rendering_entry(main[:, 0:3], main[:, 3], main[:, 4], weights, extras, prefix, posts.sdist, rgbs, getattr(cfg, 'vis_num_rays', 16)))
             if want_history:
-                hist = dict(coord=coord.reshape(prefix + (S, 3)), density=density.reshape(prefix + (S,)),
-                            rgb=(level_rgb if level_rgb is not None
-                                 else torch.zeros(N, S, 3, device=dev)).reshape(prefix + (S, 3)),
-                            raw_grad_density=None, grad_pred=None, normals=None, normals_pred=None, roughness=None,
-                            sdist=sdist.reshape(prefix + (S + 1,)).clone(), weights=weights.reshape(prefix + (S,)).clone())
-                ray_history.append(hist)
-            sdist_prev, weights_prev, n_prev = sdist, weights, S
+                ray_history.append(ml.history_entry(coord, density, rgbs, posts.sdist, weights, prefix))
 
         if compute_extras:                                             # ref models.py:313-324
-            final = (renderings[-1]['ray_rgbs'] * renderings[-1]['ray_weights'][..., None]).sum(dim=-2)
-            for r in renderings[:-1]:
-                r['ray_rgbs'] = final[:, None, :].expand(r['ray_rgbs'].shape)
+            ml.broadcast_final(renderings)
 
+        o, d, cam, far = rays.o, rays.d, rays.cam, rays.far
         if getattr(cfg, 'model_sky', False):                           # ref models.py:326-337
             # inference under an active bf16 autocast: the sky NeRF's nn.Linear layers are bf16 in the reference
             sky_mixed = bool(self.autocast_render and torch.is_autocast_enabled()

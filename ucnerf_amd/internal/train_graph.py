@@ -24,6 +24,7 @@ import torch.nn.functional as F
 
 from .. import _lib
 from . import dense_f32
+from . import march_level as ml
 
 EPS = float(torch.finfo(torch.float32).eps)
 
@@ -38,15 +39,15 @@ class _GradChannel:
 
 
 class _FieldFeatures(torch.autograd.Function):
-    """features[N*S, L*C] = HIP featurisation of one level; backward scatters into the table gradient.  `geom` = (sdist, near, far,
-    origins, directions, basis, radii, flip, spin), or with a warped Model.raydist_fn (tdist, origins, ...): the `_tdist` entry points."""
+    """features[N*S, L*C] = HIP featurisation of one level; backward scatters into the table gradient.  `posts` (march_level.Fenceposts)
+    with `rays`, `flip` and `spin` is the geometry, and picks the entry points (the metric-fencepost siblings for a warped Model.raydist_fn)."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
-    def forward(ctx, embeddings, mlp, geom, N, S, std_scale, lpb, half_table=False, chan=None):
+    def forward(ctx, embeddings, mlp, posts, rays, flip, spin, S, std_scale, lpb, half_table=False, chan=None):
         lib = _lib.load()
         desc = mlp.grid_field()
-        L, C = mlp.encoder.num_levels, mlp.encoder.level_dim
+        N, L, C = rays.N, mlp.encoder.num_levels, mlp.encoder.level_dim
         ctx.chan = chan
         layout = 1 | _lib.RAYS_INCOHERENT               # a training batch is random rays (datasets.py:278): see include/ucnerf_march.h
         if half_table:
@@ -61,10 +62,10 @@ class _FieldFeatures(torch.autograd.Function):
         feat = torch.empty(N * S, L * C, device=embeddings.device)
         coord = torch.empty(N, S, 3, device=embeddings.device)
         tmean = torch.empty(N, S, device=embeddings.device)
-        march_features = lib.ucn_march_features if len(geom) == 9 else lib.ucn_march_features_tdist
-        _lib.check(march_features(ctypes.byref(desc), *[_lib.ptr(t) for t in geom], float(std_scale), N, S,
-                                          int(lpb), layout, feat.data_ptr(), coord.data_ptr(), tmean.data_ptr(), _lib.stream()))
-        ctx.mlp, ctx.geom, ctx.dims = mlp, geom, (N, S, float(std_scale), int(lpb))
+        _lib.check(posts.entry(lib, 'ucn_march_features')(
+            ctypes.byref(desc), *posts.geometry(rays, flip, spin), float(std_scale), N, S, int(lpb), layout,
+            feat.data_ptr(), coord.data_ptr(), tmean.data_ptr(), _lib.stream()))
+        ctx.mlp, ctx.posts, ctx.cones, ctx.dims = mlp, posts, (rays, flip, spin), (N, S, float(std_scale), int(lpb))
         # the autocast step (half tables): the table gradient's row blocks accumulate in guaranteed-range fixed point (order-
         # independent, one LDS add per channel pair); the fp32 step keeps exact fp32 adds (include/ucnerf_march.h UCN_BWD_FIXED_POINT)
         ctx.fixed = bool(half_table) and bool(getattr(mlp, 'bwd_fixed_point', True))
@@ -106,11 +107,10 @@ class _FieldFeatures(torch.autograd.Function):
             else:
                 g, layout = g.contiguous(), 1
         ws = torch.empty(lib.ucn_march_features_backward_ws_floats(ctypes.byref(mlp.grid_field()), N, S), device=g.device)
-        backward = lib.ucn_march_features_backward if len(ctx.geom) == 9 else lib.ucn_march_features_backward_tdist
-        _lib.check(backward(ctypes.byref(mlp.grid_field()), *[_lib.ptr(t) for t in ctx.geom], std_scale,
-                                                   N, S, 0, layout | (_lib.BWD_FIXED_POINT if ctx.fixed else 0), g.data_ptr(), grad.data_ptr(),
-                                                   ws.data_ptr(), _lib.stream()))
-        return grad, None, None, None, None, None, None, None, None
+        _lib.check(ctx.posts.entry(lib, 'ucn_march_features_backward')(
+            ctypes.byref(mlp.grid_field()), *ctx.posts.geometry(*ctx.cones), std_scale, N, S, 0, layout | (_lib.BWD_FIXED_POINT if ctx.fixed else 0),
+            g.data_ptr(), grad.data_ptr(), ws.data_ptr(), _lib.stream()))
+        return (grad,) + (None,) * 10
 
 
 class GradientScaler(torch.autograd.Function):
@@ -993,20 +993,21 @@ def _zeros_ro(n, k, device):
 class _Composite(torch.autograd.Function):
     """render.py:155-174 + :203-216 as the rendering kernel `ucn_composite` (forward) and `ucn_composite_backward`:
     weights, rgb, depth, acc of N rays from density [N,S] and rgbs [N,S,3]; sample positions carry no gradient.
-    tdist (a warped Model.raydist_fn): the metric fenceposts, read by the `_tdist` entry points instead of sdist / near."""
+    `posts` (march_level.Fenceposts) picks the entry points (the siblings on the metric fenceposts of a warped Model.raydist_fn)."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
-    def forward(ctx, density, rgbs, sdist, near, far, dirs, bg, opaque, tdist=None):
+    def forward(ctx, density, rgbs, posts, dirs, bg, opaque):
         lib = _lib.load()
         N, S = density.shape
         density, rgbs = density.contiguous(), rgbs.contiguous()
         weights = torch.empty(N, S, device=density.device)
         main = torch.empty(N, 5, device=density.device)
-        _lib.check(_composite_call(lib, density, rgbs, sdist, near, far, tdist, dirs, float(bg), int(bool(opaque)), N, S, weights,
-                                   main, None))
-        ctx.save_for_backward(density, rgbs, sdist, near, far, dirs, tdist)
         ctx.consts = (float(bg), int(bool(opaque)))
+        _lib.check(posts.entry(lib, 'ucn_composite')(density.data_ptr(), rgbs.data_ptr(), *posts.compositing(), dirs.data_ptr(),
+                                                     *ctx.consts, N, S, weights.data_ptr(), main.data_ptr(), None, _lib.stream()))
+        ctx.save_for_backward(density, rgbs, dirs)
+        ctx.posts = posts
         # outputs nobody differentiates (depth and acc always, rgb at a proposal level) arrive as None in backward instead of as
         # zero tensors autograd fills first: 12 launches per step less (tools/train_launch_sites.py)
         ctx.set_materialize_grads(False)
@@ -1016,10 +1017,10 @@ class _Composite(torch.autograd.Function):
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, g_w, g_rgb, g_depth, g_acc):
         lib = _lib.load()
-        density, rgbs, sdist, near, far, dirs, tdist = ctx.saved_tensors
+        density, rgbs, dirs = ctx.saved_tensors
         N, S = density.shape
         if g_w is None and g_rgb is None and g_depth is None and g_acc is None:
-            return None, None, None, None, None, None, None, None, None
+            return None, None, None, None, None, None
         if g_depth is None and g_acc is None:
             # the usual case: one cat against a cached block of zeros (read-only) instead of a fill and up to three strided copies
             g_main = _zeros_ro(N, 5, density.device) if g_rgb is None else torch.cat([g_rgb.float(), _zeros_ro(N, 2, density.device)], dim=1)
@@ -1034,25 +1035,11 @@ class _Composite(torch.autograd.Function):
         g_w = None if g_w is None else g_w.float().contiguous()
         g_density = torch.empty_like(density)
         g_rgbs = torch.empty_like(rgbs)
-        if tdist is None:
-            _lib.check(lib.ucn_composite_backward(density.data_ptr(), rgbs.data_ptr(), sdist.data_ptr(), near.data_ptr(),
-                                                  far.data_ptr(), dirs.data_ptr(), *ctx.consts, N, S, _lib.ptr(g_w),
-                                                  g_main.data_ptr(), g_density.data_ptr(), g_rgbs.data_ptr(), _lib.stream()))
-        else:
-            _lib.check(lib.ucn_composite_backward_tdist(density.data_ptr(), rgbs.data_ptr(), tdist.data_ptr(), dirs.data_ptr(),
-                                                        *ctx.consts, N, S, _lib.ptr(g_w), g_main.data_ptr(), g_density.data_ptr(),
-                                                        g_rgbs.data_ptr(), _lib.stream()))
-        return g_density, g_rgbs, None, None, None, None, None, None, None
-
-
-def _composite_call(lib, density, rgbs, sdist, near, far, tdist, dirs, bg, opaque, N, S, weights, main, extras):
-    """ucn_composite, or ucn_composite_tdist on the metric fenceposts of a warped curve (far stays the batch's metric far)."""
-    if tdist is None:
-        return lib.ucn_composite(density.data_ptr(), rgbs.data_ptr(), sdist.data_ptr(), near.data_ptr(), far.data_ptr(),
-                                 dirs.data_ptr(), bg, opaque, N, S, weights.data_ptr(), main.data_ptr(), _lib.ptr(extras),
-                                 _lib.stream())
-    return lib.ucn_composite_tdist(density.data_ptr(), rgbs.data_ptr(), tdist.data_ptr(), far.data_ptr(), dirs.data_ptr(), bg,
-                                   opaque, N, S, weights.data_ptr(), main.data_ptr(), _lib.ptr(extras), _lib.stream())
+        posts = ctx.posts
+        _lib.check(posts.entry(lib, 'ucn_composite_backward')(
+            density.data_ptr(), rgbs.data_ptr(), *posts.compositing(backward=True), dirs.data_ptr(), *ctx.consts, N, S,
+            _lib.ptr(g_w), g_main.data_ptr(), g_density.data_ptr(), g_rgbs.data_ptr(), _lib.stream()))
+        return g_density, g_rgbs, None, None, None, None
 
 
 class _HashDecay(torch.autograd.Function):
@@ -1437,27 +1424,15 @@ def brightness_forward(bc, idx, which="latent_code"):
 def march_train(model, rand, batch, train_frac, compute_extras, eval_camidx, glo_vec=None):
     """Model.forward with an autograd graph (ref models.py:97-365).  glo_vec [N, num_glo_features] (or None): the NeRF level's
     per-ray GLO codes (models.py:118-127); the proposal levels get none (models.py:226)."""
-    from .models import _f32, _u_table, s_to_t
     lib = _lib.load()
     model.last_march_route = 'train_graph'
-    origins = batch['origins']
-    _lib.require_device(origins, "batch['origins']")
-    dev = origins.device
-    prefix = tuple(origins.shape[:-1])
-    N = int(np.prod(prefix))
-    o, d = _f32(origins, N, 3), _f32(batch['directions'], N, 3)
-    vd, cam = _f32(batch['viewdirs'], N, 3), _f32(batch['cam_dirs'], N, 3)
-    rad, near, far = _f32(batch['radii'], N, 1), _f32(batch['near'], N, 1), _f32(batch['far'], N, 1)
-    pinned_vec = batch.get('rand_vec')
-    if pinned_vec is not None:
-        pinned_vec = _f32(pinned_vec, N, 3 * model.num_levels)
-    pinned = batch.get('march_noise')
-    st = _lib.stream()
-    cfg = model.config
-    anneal = (model.anneal_slope * train_frac) / ((model.anneal_slope - 1) * train_frac + 1) if model.anneal_slope > 0 else 1.
+    rays = ml.Rays(batch, model.num_levels)
+    N, dev, prefix = rays.N, rays.dev, rays.prefix
+    o, d, vd, cam, far = rays.o, rays.d, rays.vd, rays.cam, rays.far
+    st, cfg = _lib.stream(), model.config
+    bg, opaque = float(model.bg_intensity_range[0]), int(bool(model.opaque_background))
     renderings, ray_history = [], []
-    sdist_prev = weights_prev = None
-    n_prev, prod = 0, 1
+    posts = weights = None
     # The sky NeRF depends on the rays only, not on the field: with `Model.sky_side_stream` its fused forward is issued FIRST, on
     # a second HIP stream, and joins at the colour-correction step.  Autograd runs a node's backward on the stream of its
     # forward, so the sky's compositing backward, dgrad kernel and weight-gradient passes (HBM-bound: 4.4 GB of stores, 9 GB of
@@ -1471,86 +1446,35 @@ def march_train(model, rand, batch, train_frac, compute_extras, eval_camidx, glo
             _sky_pending = sky_forward_fused(model.skynerf, o, d, cam, far)
         for t in (o, d, cam, far):
             t.record_stream(model._sky_stream)
-    for i_level in range(model.num_levels):
-        is_prop = i_level < model.num_levels - 1
-        S = model.num_prop_samples if is_prop else model.num_nerf_samples
-        mlp = model.get_submodule(f'prop_mlp_{i_level}') if is_prop else model.nerf_mlp
-        dilation = model.dilation_bias + model.dilation_multiplier * 1.0 / prod
-        if not (model.dilation_bias > 0 or model.dilation_multiplier > 0):
-            dilation = 0.0                                               # ref models.py:167 use_dilation False
-        elif not dilation > 0:
-            raise NotImplementedError(f"dilation {dilation} <= 0 with use_dilation on (a negative dilation_bias): ucn_resample "
-                                      "takes dilation <= 0 as the reference's UNdilated branch")
-        prod *= S
-        jitter = flip = spin = None
-        u_tab, max_jitter = _u_table(S, bool(rand), dev)
-        if rand:
-            pn = pinned[i_level] if pinned is not None else {}
-            jcols = 1 if model.single_jitter else S
-            jitter = _f32(pn['jitter'], N, jcols) if 'jitter' in pn else torch.rand(N, jcols, device=dev)
-            flip = _f32(pn['flip'], N, S) if 'flip' in pn else torch.rand(N, S, device=dev)
-            spin = _f32(pn['spin'], N, S) if 'spin' in pn else torch.rand(N, S, device=dev)
-        rvec = (pinned_vec[:, 3 * i_level:3 * i_level + 3].contiguous() if pinned_vec is not None
-                else torch.randn(N, 3, device=dev))
-        sdist = torch.empty(N, S + 1, device=dev)
-        basis = torch.empty(N, 6, device=dev)
-        wp = None if weights_prev is None else weights_prev.detach().contiguous()
-        _lib.check(lib.ucn_resample(_lib.ptr(sdist_prev), _lib.ptr(wp), n_prev, dilation, anneal,
-                                    float(model.resample_padding), u_tab.data_ptr(), _lib.ptr(jitter),
-                                    0 if jitter is None else jitter.shape[1], max_jitter, N, S, sdist.data_ptr(), st))
-        pn_s = (pinned[i_level] if pinned is not None else {}).get('sdist') if rand else None
-        if pn_s is not None:
-            # test hook, like the pinned random draws: this level's sample fenceposts handed in by the caller instead of the
-            # resampling kernel's -- tests/test_train_full_size.py uses it to separate "1-ulp sample positions amplified by 2^19-wide
-            # levels" from anything the backward could be doing wrong.  No gradient flows through the fenceposts in the reference
-            # either (stepfun.py:251-294 works on detached weights).
-            sdist = _f32(pn_s, N, S + 1).clone()
-        _lib.check(lib.ucn_cone_basis(cam.data_ptr(), rvec.data_ptr(), N, basis.data_ptr(), st))
-        tdist = s_to_t(model, sdist, near, far, st)              # a warped raydist_fn: metric fenceposts (models.py:208), else None
-        geom = ((sdist, near, far) if tdist is None else (tdist,)) + (o, d, basis, rad, flip, spin)
+    for i_level, is_prop, S, mlp, dilation in ml.level_plan(model):
+        # 'sdist' among the pinned draws (tests/test_train_full_size.py): tells 1-ulp sample positions amplified by 2^19-wide levels from a wrong backward
+        posts, flip, spin = ml.fenceposts(model, rays, i_level, S, dilation, train_frac, rand, posts, weights, st,
+                                          pinned_sdist=rays.noise[i_level].get('sdist') if rand else None)
         half_table = torch.is_autocast_enabled() and mlp.encoder.level_dim % 2 == 0 and getattr(model, 'autocast_half_tables', True)
         chan = _GradChannel()                        # `feat` has exactly one consumer, the heads below: the two nodes may agree on its gradient's layout
-        feat, coord, tmean = _FieldFeatures.apply(mlp.encoder.embeddings, mlp, geom, N, S, model.std_scale,
+        feat, coord, tmean = _FieldFeatures.apply(mlp.encoder.embeddings, mlp, posts, rays, flip, spin, S, model.std_scale,
                                                   model.levels_per_block, half_table, chan)
         glo = None if (is_prop or glo_vec is None) else mlp.glo_affine(glo_vec.reshape(N, -1))
         density, rgbs = field_heads(mlp, feat, vd, N, S, chan, glo)
         if getattr(cfg, 'brightness_correction', False):              # models.py:233-235 (gated on this flag)
             rgbs, density = GradientScaler.apply(rgbs, density, tmean)
-        weights, c_rgb, c_depth, c_acc = _Composite.apply(density, rgbs, sdist, near, far, d,
-                                                          float(model.bg_intensity_range[0]), model.opaque_background, tdist)
-        rendering = dict(rgb=c_rgb, depth=c_depth, acc=c_acc)
-        rendering = {k: v.reshape(prefix + v.shape[1:]) for k, v in rendering.items()}
-        rendering['weights'] = weights.reshape(prefix + (S,))
+        weights, c_rgb, c_depth, c_acc = _Composite.apply(density, rgbs, posts, d, bg, opaque)
+        extras = None
         if compute_extras:
             # render.py:218-242: depth percentiles and the mean distance -- not differentiated by any loss of the path
             # (train_utils.py reads them for metrics only), so they come from the rendering kernel on detached inputs
             with torch.no_grad():
                 dn, rg = density.detach().float().contiguous(), rgbs.detach().float().contiguous()
                 w_x, main_x, extras = torch.empty(N, S, device=dev), torch.empty(N, 5, device=dev), torch.empty(N, 4, device=dev)
-                _lib.check(_composite_call(lib, dn, rg, sdist, near, far, tdist, d, float(model.bg_intensity_range[0]),
-                                           int(bool(model.opaque_background)), N, S, w_x, main_x, extras))
-            rendering['distance_mean'] = extras[:, 0].reshape(prefix)
-            rendering['distance_percentile_5'] = extras[:, 1].reshape(prefix)
-            rendering['distance_median'] = extras[:, 2].reshape(prefix)
-            rendering['distance_percentile_95'] = extras[:, 3].reshape(prefix)
-            n_vis = getattr(cfg, 'vis_num_rays', 16)
-            rendering['ray_sdist'] = sdist[:n_vis]
-            rendering['ray_weights'] = weights[:n_vis]
-            rendering['ray_rgbs'] = rgbs[:n_vis]
-        hist = dict(coord=coord.reshape(prefix + (S, 3)), density=density.reshape(prefix + (S,)),
-                    rgb=rgbs.reshape(prefix + (S, 3)), raw_grad_density=None, grad_pred=None, normals=None,
-                    normals_pred=None, roughness=None)
+                _lib.check(posts.entry(lib, 'ucn_composite')(dn.data_ptr(), rg.data_ptr(), *posts.compositing(), d.data_ptr(), bg,
+                                                             opaque, N, S, w_x.data_ptr(), main_x.data_ptr(), extras.data_ptr(), st))
+        renderings.append(ml.rendering_entry(c_rgb, c_depth, c_acc, weights, extras, prefix, posts.sdist, rgbs, getattr(cfg, 'vis_num_rays', 16)))
+        hist = ml.history_entry(coord, density, rgbs, posts.sdist, weights, prefix)
         if model.training:
             hist['loss_hash_decay'] = hash_decay(mlp)
-        hist['sdist'] = sdist.reshape(prefix + (S + 1,)).clone()
-        hist['weights'] = weights.reshape(prefix + (S,)).clone()
-        renderings.append(rendering)
         ray_history.append(hist)
-        sdist_prev, weights_prev, n_prev = sdist, weights, S
     if compute_extras:
-        final = (renderings[-1]['ray_rgbs'] * renderings[-1]['ray_weights'][..., None]).sum(dim=-2)
-        for r in renderings[:-1]:
-            r['ray_rgbs'] = final[:, None, :].expand(r['ray_rgbs'].shape)
+        ml.broadcast_final(renderings)
     with_sky = getattr(cfg, 'model_sky', False)
     if with_sky:
         # under bf16 autocast (what train.py:165 runs): the hand-written sky kernels; else the eager fp32 form (the G10 parity path)
