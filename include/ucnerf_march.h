@@ -95,6 +95,15 @@ typedef struct ucn_field {
      * 1: split-f16 MFMA (hi/lo f16 operands, 3 x v_mfma_f32_32x32x16_f16, fp32 accumulate; ~3e-7
      *    relative per product).  Must be the same at ucn_field_pack and ucn_field_mlp time. */
     uint32_t mlp_mode;
+    /* ABI 28 (MLP.scale_featurization, models.py:436-437): the density MLP reads n_scale_planes pseudo-level planes
+     * [n_scale_planes][B][level_dim] behind the [num_levels][B][level_dim] grid planes of its feature buffer (what
+     * ucn_march_scale_features / ucn_points_scale_features write), and w_d0 is [64, (num_levels + n_scale_planes) * level_dim]
+     * (the reference's [64, L*C + L] right-padded with zero columns).  0 = no scale features: a zero-initialised descriptor
+     * behaves as before.  The featurisation and table-gradient kernels ignore it (they keep the grid width).
+     * scale_init_std: the encoder's init_std (the constant under the root of k[l]); mlp_mode 1 bounds the scale inputs by
+     * sqrt(scale_init_std^2 + level_dim * max|table|^2) when it picks its layer scales.  Read only with n_scale_planes > 0. */
+    float scale_init_std;
+    uint32_t n_scale_planes;
 } ucn_field_t;
 
 uint64_t ucn_field_packed_floats(const ucn_field_t *f);
@@ -251,6 +260,35 @@ int ucn_contract_probe(const float *means, const float *stds, uint32_t B, float 
 int ucn_points_features(const ucn_field_t *f, const float *means, const float *stds, uint32_t B,
                         uint32_t G, int warp, uint32_t levels_per_block, float *features_out /*[L][B][C]*/,
                         float *coord_out /*[B,3]|NULL*/, ucn_stream_t stream);
+
+/* ------------------------------------------------- scale featurization (ABI 28; ref: models.py:436-437, :497-506)
+ * One extra density-MLP input per grid level l of a sample:  (2 mean_j w[j, l] - 1) * k[l],  w[j, l] = the erf damping
+ * ucn_march_features applies to multisample j (same Gaussians, same erf, same int32-wrapped grid_sizes^2) and
+ * k[l] = sqrt(init_std^2 + mean over level l's rows of sum_c embeddings[row, c]^2).
+ *
+ * ucn_level_scale: k [L] on the device, from the fp32 table.  Two passes of fixed summation order, no float atomics:
+ * bit-reproducible from run to run.  No host read-back.  workspace: DEVICE, UCN_LEVEL_SCALE_WS_FLOATS floats. */
+#define UCN_LEVEL_SCALE_WS_FLOATS (UCN_MAX_LEVELS * 64)
+int ucn_level_scale(const float *embeddings /*[rows, C]*/, const int32_t *offsets_host /*HOST [L+1]*/, uint32_t L, uint32_t C,
+                    float init_std, float *out /*DEVICE [L]*/, float *workspace, ucn_stream_t stream);
+/* The scale features of the samples ucn_march_features featurises (ray arguments as there; f: the grid part only; no table
+ * access).  layout 1: scale_out [N*S][L], sample-major (the training graph).  layout 0 / 2: ceil(L/C) pseudo-level planes
+ * [ceil(L/C)][N*S][C] with b ordered as in ucn_march_features' layout 0 (b = ray*S + s) / 2 (b = s*N + ray); plane p,
+ * channel c holds level p*C + c, channels past L are written as 0.  Pass scale_out = features + L*N*S*C to place them
+ * directly behind the gather's planes: ucn_field_mlp then reads one [L + ceil(L/C)][N*S][C] buffer (ucn_field_t::n_scale_planes). */
+int ucn_march_scale_features(const ucn_field_t *f, const float *sdist, const float *near_, const float *far_,
+                             const float *origins, const float *directions, const float *basis, const float *radii,
+                             const float *flip, const float *spin, float std_scale, uint32_t N, uint32_t S,
+                             const float *level_scale /*DEVICE [L]*/, int layout, float *scale_out, ucn_stream_t stream);
+/* ... on metric fenceposts (see ucn_march_features_tdist); bit-identical on the identity curve's tdist. */
+int ucn_march_scale_features_tdist(const ucn_field_t *f, const float *tdist, const float *origins, const float *directions,
+                                   const float *basis, const float *radii, const float *flip, const float *spin,
+                                   float std_scale, uint32_t N, uint32_t S, const float *level_scale, int layout,
+                                   float *scale_out, ucn_stream_t stream);
+/* ... for caller-supplied Gaussians, beside ucn_points_features (means [B,G,3], stds [B,G], mean over the G Gaussians):
+ * sample_major 0: [ceil(L/C)][B][C] planes, 1: [B][L]. */
+int ucn_points_scale_features(const ucn_field_t *f, const float *means, const float *stds, uint32_t B, uint32_t G, int warp,
+                              const float *level_scale, int sample_major, float *scale_out, ucn_stream_t stream);
 
 /* ref: coord.py:214-225 pos_enc(viewdirs): the per-ray direction inputs of the colour MLP.
  * mlp_mode 0: folded through the direction columns of lin_second_stage_{0,1} into additive terms

@@ -11,7 +11,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # UCN_LIB_PATH: another build of the same ABI for A/B measurements; default = the in-tree product
 LIB_PATH = os.environ.get("UCN_LIB_PATH") or os.path.join(_HERE, "csrc", "libucnerf_march.so")
-ABI_VERSION = 27
+ABI_VERSION = 28
 LAUNCH_CORESIDENT = 0x100
 TABLE_F16 = 0x200
 RAYS_INCOHERENT = 0x1000   # ucn_march_features layout flag: random (training) rays -> lane-paired fetch on every hashed level
@@ -19,6 +19,7 @@ GFEAT_LEVEL_MAJOR4 = 0x20000  # ... for level_dim 4: [F / 4][M][4], / 6
 GFEAT_LEVEL_MAJOR = 0x10000  # ucn_train_bwd F flag: gfeat as [F / 2][M][2], / 6 = ucn_march_features_backward's layout 4 (include/ucnerf_march.h)
 BWD_FIXED_POINT = 0x800    # ucn_march_features_backward layout flag: int32 fixed-point row blocks (include/ucnerf_march.h UCN_BWD_FIXED_POINT)
 FEATURES_BF16 = 0x400      # ucn_march_features layout flag: features as [L][B] bf16 pairs (half tables, level_dim 2)
+LEVEL_SCALE_WS_FLOATS = 24 * 64  # include/ucnerf_march.h UCN_LEVEL_SCALE_WS_FLOATS
 FEAT_BF16 = 0x100          # ucn_train_fwd feat_level_dim flag: the features are those pairs          # include/ucnerf_march.h UCN_LAUNCH_CORESIDENT
 
 c_u32, c_u64, c_i32, c_f32, c_vp = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int, ctypes.c_float, ctypes.c_void_p
@@ -37,6 +38,7 @@ class UcnField(ctypes.Structure):
         ("density_bias", c_f32), ("rgb_premultiplier", c_f32), ("rgb_bias", c_f32), ("rgb_padding", c_f32),
         ("packed", c_vp),
         ("mlp_mode", c_u32),
+        ("scale_init_std", c_f32), ("n_scale_planes", c_u32),
     ]
 
 
@@ -88,6 +90,12 @@ SIGNATURES = {
     "ucn_cast_probe_tdist": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_u32, c_u32, c_vp, c_vp],
     "ucn_contract_probe": [c_vp, c_vp, c_u32, c_vp, c_vp, c_vp],
     "ucn_points_features": [ctypes.POINTER(UcnField), c_vp, c_vp, c_u32, c_u32, c_i32, c_u32, c_vp, c_vp, c_vp],
+    "ucn_level_scale": [c_vp, c_vp, c_u32, c_u32, c_f32, c_vp, c_vp, c_vp],
+    "ucn_march_scale_features": [ctypes.POINTER(UcnField), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_u32, c_u32,
+                                 c_vp, c_i32, c_vp, c_vp],
+    "ucn_march_scale_features_tdist": [ctypes.POINTER(UcnField), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_u32, c_u32, c_vp,
+                                       c_i32, c_vp, c_vp],
+    "ucn_points_scale_features": [ctypes.POINTER(UcnField), c_vp, c_vp, c_u32, c_u32, c_i32, c_vp, c_i32, c_vp, c_vp],
     "ucn_field_dir_floats": [ctypes.POINTER(UcnField), c_u32],
     "ucn_field_dir_bias": [ctypes.POINTER(UcnField), c_vp, c_u32, c_vp, c_vp],
     "ucn_field_mlp": [ctypes.POINTER(UcnField), c_vp, c_u32, c_u32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp],

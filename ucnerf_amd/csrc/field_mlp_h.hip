@@ -182,8 +182,9 @@ __device__ __forceinline__ int scale_exponent(float bound, float typical) {
 // One workgroup.  bound_k: rigorous max |h_k| given |features| <= m0 and |direction tile| <= 1;  typ_k: sqrt of the
 // mean second moment of h_k assuming independent inputs of second moment typ_(k-1)^2 (1/2 for the direction
 // encoding), halved by the ReLU.
+// F_grid < F: inputs F_grid.. are scale features (scale_featurization), bounded by k[l] <= sqrt(init_std^2 + C m0^2) instead of m0
 __global__ __launch_bounds__(256) void k_field_scales(const float *__restrict__ Wd0, const float *__restrict__ bd0, uint32_t F,
-                                                      const float *__restrict__ MA, const float *__restrict__ MB,
+                                                      uint32_t F_grid, uint32_t C, float init_std, const float *__restrict__ MA, const float *__restrict__ MB,
                                                       const float *__restrict__ Wc1, uint32_t ldc1, uint32_t NW, uint32_t ND,
                                                       const uint32_t *__restrict__ m0_bits, int *__restrict__ exps,
                                                       float *__restrict__ side, float *__restrict__ report) {
@@ -205,9 +206,16 @@ __global__ __launch_bounds__(256) void k_field_scales(const float *__restrict__ 
     float bnd = 0.0f, sq = 0.0f, b_h0, t_h0, b_h1, t_h1, b_h2, t_h2;
     if (t < 64u) {
         float sa = 0.0f, s2 = 0.0f;
-        for (uint32_t j = 0; j < F; j++) { const float w = Wd0[t * F + j]; sa += fabsf(w); s2 += w * w; }
+        for (uint32_t j = 0; j < F_grid; j++) { const float w = Wd0[t * F + j]; sa += fabsf(w); s2 += w * w; }
         bnd = sa * m0 + fabsf(bd0[t]);
         sq = s2 * t0 * t0 + bd0[t] * bd0[t];
+        if (F_grid < F) {
+            const float ms = sqrtf(init_std * init_std + (float)C * m0 * m0) * 1.000001f;          // (the roundings of this line)
+            sa = s2 = 0.0f;
+            for (uint32_t j = F_grid; j < F; j++) { const float w = Wd0[t * F + j]; sa += fabsf(w); s2 += w * w; }
+            bnd += sa * ms;
+            sq += s2 * (0.5f * ms) * (0.5f * ms);
+        }
     }
     reduce(bnd, sq, 64u, b_h0, t_h0);
     auto composed = [&](const float *M, float &b_out, float &q_out) {
@@ -710,8 +718,8 @@ int ucn_h_pack(const ucn_field_t *f, const PackPlan &pl, hipStream_t st) {
     // layer scales
     const uint64_t n_emb = (uint64_t)f->offsets_host[f->num_levels] * f->level_dim;
     hipLaunchKernelGGL(k_absmax, dim3(1024), dim3(256), 0, st, f->embeddings, n_emb, reinterpret_cast<uint32_t *>(scratch));
-    hipLaunchKernelGGL(k_field_scales, dim3(1), dim3(256), 0, st, f->w_d0, f->b_d0, pl.F, MA, MB, f->w_c1, NW + NB + ND, NW, ND,
-                       reinterpret_cast<const uint32_t *>(scratch), exps, side, scratch + 8);
+    hipLaunchKernelGGL(k_field_scales, dim3(1), dim3(256), 0, st, f->w_d0, f->b_d0, pl.F, f->num_levels * f->level_dim, f->level_dim, f->scale_init_std,
+                       MA, MB, f->w_c1, NW + NB + ND, NW, ND, reinterpret_cast<const uint32_t *>(scratch), exps, side, scratch + 8);
     hipLaunchKernelGGL(k_pack_side, dim3(ucn_div_up(256u + NW * 4u, 256)), dim3(256), 0, st, f->b_d0, f->w_d1, f->b_d1, f->w_rgb, NW,
                        exps, side);
     uint64_t g = 0;                                                     // position in groups

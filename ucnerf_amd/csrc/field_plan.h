@@ -36,8 +36,11 @@ static inline uint32_t dir_stride_h(uint32_t n_width) { return n_width == 256 ? 
 static inline int make_plan(const ucn_field_t *f, PackPlan *pl) {
     UCN_REQUIRE(f, "field: null descriptor");
     UCN_REQUIRE(f->mlp_mode <= 1, "field: mlp_mode must be 0 (fp32 MFMA) or 1 (split-f16 MFMA)");
-    pl->F = f->num_levels * f->level_dim;
-    UCN_REQUIRE(pl->F % 2 == 0 && pl->F >= 2, "field: num_levels*level_dim must be even, got %u", pl->F);
+    // the density MLP's input width: the grid planes and, with scale featurization, the pseudo-level planes behind them
+    UCN_REQUIRE(f->n_scale_planes == 0 || f->n_scale_planes == (f->num_levels + f->level_dim - 1) / f->level_dim,
+                "field: n_scale_planes must be 0 or ceil(num_levels / level_dim), got %u", f->n_scale_planes);
+    pl->F = (f->num_levels + f->n_scale_planes) * f->level_dim;
+    UCN_REQUIRE(pl->F % 2 == 0 && pl->F >= 2, "field: the density MLP's input width must be even, got %u", pl->F);
     pl->KQ = pl->F / 2;
     pl->prop = f->n_bottleneck == 1;
     pl->p0 = 0;
@@ -58,7 +61,8 @@ static inline int make_plan(const ucn_field_t *f, PackPlan *pl) {
         UCN_REQUIRE(f->w_c0 && f->w_c1 && f->w_rgb && f->b_c0 && f->b_c1 && f->b_rgb, "field: colour MLP weights missing");
         UCN_REQUIRE(f->n_dir >= 3 && f->n_dir <= 27, "field: n_dir must be in [3,27] (one 32-wide tile incl. the bias slot)");
         UCN_REQUIRE(f->mlp_mode == 0 || pl->F <= 16 * kFirstSteps,
-                    "field: mlp_mode 1 supports num_levels*level_dim <= %u, got %u", 16 * kFirstSteps, pl->F);
+                    "field: mlp_mode 1 supports a density MLP input of <= %u values (num_levels*level_dim, plus the scale "
+                    "feature planes of scale_featurization), got %u: use mlp_mode 0", 16 * kFirstSteps, pl->F);
         pl->NTB = f->n_bottleneck / 32;
         pl->NTW = f->n_width / 32;
         const uint32_t g0 = (stream_groups_f32(pl->NTB, pl->NTW) + kChunkGroups - 1) / kChunkGroups * kChunkGroups;

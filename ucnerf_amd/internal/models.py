@@ -11,7 +11,8 @@ composite) instead of ~300 eager ops, and nothing of size [N*S*6, .] is ever mat
 Supported configuration = the reference's shipped one (configs/waymo.gin): disable_density_normals,
 no reflections / diffuse / IDE, plus GLO appearance codes (num_glo_features > 0; DESIGN.md "GLO") and every
 ray-distance curve of coord.construct_ray_warps (raydist_fn None, 'piecewise', 'power_transformation' or a gin-bound
-torch.reciprocal / log / exp / sqrt / square; DESIGN.md "Ray-distance curves").  Anything else raises at construction.
+torch.reciprocal / log / exp / sqrt / square; DESIGN.md "Ray-distance curves") and the featurized grid scale
+(MLP.scale_featurization).  Anything else raises at construction.
 In eval mode or with gradients disabled forward is the fused inference march; a model in training mode
 with gradients enabled routes to internal/train_graph.py (same kernels for resampling and featurisation, HIP
 backward for the tables and the dense layers' dgrad, autograd glue; `Model.march_route`).  Without the HIP library or a GPU every entry point raises.
@@ -147,7 +148,7 @@ class MLP(nn.Module):
         set_kwargs(self, kwargs)
         unsupported = dict(use_reflections=False, use_directional_enc=False, enable_pred_roughness=False,
                            use_diffuse_color=False, use_specular_tint=False, use_n_dot_v=False,
-                           enable_pred_normals=False, disable_density_normals=True, scale_featurization=False,
+                           enable_pred_normals=False, disable_density_normals=True,
                            net_depth_viewdirs=2, skip_layer_dir=0, num_rgb_channels=3,
                            warp_fn='contract', bottleneck_noise=0.0, density_noise=0.0)
         for k, want in unsupported.items():
@@ -162,6 +163,8 @@ class MLP(nn.Module):
                                    desired_resolution=self.grid_disired_resolution,
                                    log2_hashmap_size=self.grid_log2_hashmap_size, gridtype='hash', align_corners=False)
         last_dim = self.encoder.output_dim
+        if self.scale_featurization:                 # ref models.py:436-437: one scale feature per grid level
+            last_dim += self.encoder.num_levels
         self.density_layer = nn.Sequential(nn.Linear(last_dim, 64), nn.ReLU(),
                                            nn.Linear(64, 1 if self.disable_rgb else self.bottleneck_width))
         self.dim_dir_enc = 3 + 6 * self.deg_view
@@ -184,7 +187,33 @@ class MLP(nn.Module):
             self.rgb_layer = nn.Linear(last_dim_rgb, self.num_rgb_channels)
         self._fields = {}          # (mlp_mode, glo fold) -> (key, ucn_field_t, packed weight stream): one packed buffer each
 
-    _UNPICKLED = ('_fields', '_grid_desc', '_grid_desc_key', '_glo_fold')
+    _UNPICKLED = ('_fields', '_grid_desc', '_grid_desc_key', '_glo_fold', '_level_scale')
+
+    # ---- scale featurization (ref models.py:436-437, :497-506) ---------------------
+    def scale_planes(self):
+        """Pseudo-level planes the scale features occupy behind the grid planes of a level-major feature buffer: ceil(L / C)
+        (plane p, channel c = the scale feature of level p*C + c), 0 without scale_featurization."""
+        enc = self.encoder
+        return (enc.num_levels + enc.level_dim - 1) // enc.level_dim if self.scale_featurization else 0
+
+    @torch.no_grad()
+    def level_scale(self):
+        """k [L] on the device: sqrt(init_std^2 + per-level mean of sum_c embeddings^2) of the fp32 table (models.py:498-505, no
+        gradient), by ucn_level_scale.  Recomputed only when the table changed: once per render, once per training step."""
+        emb, enc = self.encoder.embeddings, self.encoder
+        _lib.require_device(emb, f"{type(self).__name__}.encoder.embeddings")
+        if emb.dtype != torch.float32 or not emb.is_contiguous():
+            raise RuntimeError("field parameters must be contiguous float32")
+        key = (emb.data_ptr(), emb._version)
+        hit = getattr(self, '_level_scale', None)
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        out = torch.empty(enc.num_levels, device=emb.device)
+        ws = torch.empty(_lib.LEVEL_SCALE_WS_FLOATS, device=emb.device)
+        _lib.check(_lib.load().ucn_level_scale(emb.data_ptr(), enc._offsets_np.ctypes.data, enc.num_levels, enc.level_dim,
+                                               float(enc.init_std), out.data_ptr(), ws.data_ptr(), _lib.stream()))
+        self._level_scale = (key, out)
+        return out
 
     # ---- GLO appearance codes (ref models.py:600-614) ---------------------------------------------
     def uses_glo(self):
@@ -277,6 +306,15 @@ class MLP(nn.Module):
         d.density_bias, d.rgb_premultiplier = float(self.density_bias), float(self.rgb_premultiplier)
         d.rgb_bias, d.rgb_padding = float(self.rgb_bias), float(self.rgb_padding)
         d.mlp_mode = mode
+        w_d0 = None
+        if self.scale_featurization:
+            # the kernels read [L + ceil(L/C)] planes of C: density_layer.0's [64, L*C + L] right-padded with zero columns to
+            # that width (the padding channels of the last scale plane), rebuilt with the packed copy under the same key
+            d.n_scale_planes, d.scale_init_std = self.scale_planes(), float(enc.init_std)
+            with torch.no_grad():
+                w_d0 = torch.zeros(ws[1].shape[0], (enc.num_levels + d.n_scale_planes) * enc.level_dim, device=ws[1].device)
+                w_d0[:, :ws[1].shape[1]] = ws[1]
+            d.w_d0 = w_d0.data_ptr()
         n = lib.ucn_field_packed_floats(ctypes.byref(d))
         if n == 0:
             raise RuntimeError(lib.ucn_last_error().decode())
@@ -285,7 +323,7 @@ class MLP(nn.Module):
             packed = torch.empty(n, dtype=torch.float32, device=ws[0].device)
         d.packed = packed.data_ptr()
         _lib.check(lib.ucn_field_pack(ctypes.byref(d), _lib.stream()))
-        self._fields[mode_key] = (key, d, packed)
+        self._fields[mode_key] = (key, d, packed, w_d0)        # (w_d0: kept alive for mode 0, whose kernels are not its only readers)
         return d
 
     def grid_field(self):
@@ -362,11 +400,14 @@ class MLP(nn.Module):
         m = _f32(means, B * G, 3)
         s = _f32(stds, B * G, 1)
         L, C = self.encoder.num_levels, self.encoder.level_dim
-        feat = torch.empty(L * B * C, device=dev)
+        feat = torch.empty((L + self.scale_planes()) * B * C, device=dev)
         coord = torch.empty(B, 3, device=dev)
         st = _lib.stream()
         _lib.check(lib.ucn_points_features(ctypes.byref(d), m.data_ptr(), s.data_ptr(), B, G, 0 if no_warp else 1, 1,
                                            feat.data_ptr(), coord.data_ptr(), st))
+        if self.scale_featurization:               # the scale planes, behind the grid planes
+            _lib.check(lib.ucn_points_scale_features(ctypes.byref(d), m.data_ptr(), s.data_ptr(), B, G, 0 if no_warp else 1,
+                                                     self.level_scale().data_ptr(), 0, feat[L * B * C:].data_ptr(), st))
         density = torch.empty(B, device=dev)
         n_out = 1 if self.disable_rgb else self.bottleneck_width
         x = torch.empty(B, n_out, device=dev) if (want_x and not self.disable_rgb) else None
@@ -550,6 +591,8 @@ class Model(nn.Module):
         kernels need -- the half table behind a copy of the grid descriptor and the packed / rounded dense parameters."""
         if not (self.autocast_render and torch.is_autocast_enabled() and torch.get_autocast_dtype('cuda') == torch.bfloat16):
             return None
+        if mlp.scale_featurization:                # the bf16 inference kernels read grid planes only: fp32-class path (DESIGN.md 7c)
+            return None
         from . import train_graph as tg
         emb = mlp.encoder.embeddings
         probe = torch.empty(1, F_in, device=emb.device)
@@ -655,15 +698,16 @@ class Model(nn.Module):
         renderings, ray_history = [], []
         posts = weights = None
         nerf_chunk = max(1, int(self.max_chunk_rays))
-        nerf_row = self.num_nerf_samples * self.nerf_mlp.encoder.num_levels * self.nerf_mlp.encoder.level_dim
+        planes = lambda m: m.encoder.num_levels + m.scale_planes()          # feature planes of level_dim floats per sample
+        nerf_row = self.num_nerf_samples * planes(self.nerf_mlp) * self.nerf_mlp.encoder.level_dim
         for i_level, is_prop, S, mlp, dilation in ml.level_plan(self):
             desc = mlp.field(glo_fold=not is_prop)
             L, C = mlp.encoder.num_levels, mlp.encoder.level_dim
             # max_chunk_rays is quoted for the NeRF level; a proposal level (fewer samples, narrower features) takes
             # proportionally more rays per pass -- the same workspace bytes, fewer and longer launches
             chunk = nerf_chunk
-            if is_prop and S * L * C < nerf_row:
-                chunk = max(nerf_chunk, min(nerf_chunk * nerf_row // (S * L * C) // 256 * 256, 1 << 16))
+            if is_prop and S * planes(mlp) * C < nerf_row:
+                chunk = max(nerf_chunk, min(nerf_chunk * nerf_row // (S * planes(mlp) * C) // 256 * 256, 1 << 16))
             # ---- random draws and fenceposts (resample -> cone basis -> metric fenceposts of a warped raydist_fn)
             posts, flip, spin = ml.fenceposts(self, rays, i_level, S, dilation, train_frac, rand, posts, weights, st)
             march_features = posts.entry(lib, 'ucn_march_features')
@@ -675,7 +719,8 @@ class Model(nn.Module):
             extras = torch.empty(N, 4, device=dev) if compute_extras else None
             coord = torch.empty(N, S, 3, device=dev) if want_history else None
             nc = min(chunk, N)
-            feat = torch.empty(L * nc * S * C, device=dev)
+            feat = torch.empty(planes(mlp) * nc * S * C, device=dev)
+            level_scale = mlp.level_scale() if mlp.scale_featurization else None
             mixed = self._mixed_level(mlp, is_prop, L * C)
             self._mixed_levels = getattr(self, '_mixed_levels', 0) + (mixed is not None)      # diagnostics / tests
             prof = getattr(self, '_prof', None)
@@ -716,6 +761,10 @@ class Model(nn.Module):
                 _lib.check(march_features(
                     feat_desc, *posts.geometry(rays, flip, spin, sl), float(self.std_scale), n, S, int(self.levels_per_block), feat_layout,
                     fb.data_ptr(), None if coord is None else coord[sl].data_ptr(), None, fstream.cuda_stream))
+                if level_scale is not None:          # the scale planes of this pass's n * S samples, behind its L grid planes
+                    _lib.check(posts.entry(lib, 'ucn_march_scale_features')(
+                        feat_desc, *posts.geometry(rays, flip, spin, sl), float(self.std_scale), n, S, level_scale.data_ptr(),
+                        feat_layout & 3, fb[L * n * S * C:].data_ptr(), fstream.cuda_stream))
                 if timed:
                     e1.record(fstream)
                 if overlap:

@@ -113,6 +113,20 @@ class _FieldFeatures(torch.autograd.Function):
         return (grad,) + (None,) * 10
 
 
+@torch.no_grad()
+def scale_features(mlp, posts, rays, flip, spin, S, std_scale):
+    """[N*S, L] float32: the scale features of a level's samples (MLP.scale_featurization, ref models.py:497-506) from
+    ucn_march_scale_features, sample-major.  A constant of the graph, as in the reference: k is taken under no_grad, the
+    Gaussians carry no gradient (coord.py:75), so nothing flows to the table or the positions through it."""
+    lib = _lib.load()
+    N, L = rays.N, mlp.encoder.num_levels
+    out = torch.empty(N * S, L, device=rays.dev)
+    _lib.check(posts.entry(lib, 'ucn_march_scale_features')(
+        ctypes.byref(mlp.grid_field()), *posts.geometry(rays, flip, spin), float(std_scale), N, S, mlp.level_scale().data_ptr(), 1,
+        out.data_ptr(), _lib.stream()))
+    return out
+
+
 class GradientScaler(torch.autograd.Function):
     """ref train_utils.py:101-111: identity forward, grads scaled by clamp(ray_dist^2, 0, 1)."""
 
@@ -1451,9 +1465,13 @@ def march_train(model, rand, batch, train_frac, compute_extras, eval_camidx, glo
         posts, flip, spin = ml.fenceposts(model, rays, i_level, S, dilation, train_frac, rand, posts, weights, st,
                                           pinned_sdist=rays.noise[i_level].get('sdist') if rand else None)
         half_table = torch.is_autocast_enabled() and mlp.encoder.level_dim % 2 == 0 and getattr(model, 'autocast_half_tables', True)
-        chan = _GradChannel()                        # `feat` has exactly one consumer, the heads below: the two nodes may agree on its gradient's layout
+        # `feat` has exactly one consumer, the heads below: the two nodes may agree on its gradient's layout.  Not with scale
+        # featurization: the heads then read cat([feat, scale features]) and autograd hands gfeat[:, :L*C] back sample-major (layout 1)
+        chan = None if mlp.scale_featurization else _GradChannel()
         feat, coord, tmean = _FieldFeatures.apply(mlp.encoder.embeddings, mlp, posts, rays, flip, spin, S, model.std_scale,
                                                   model.levels_per_block, half_table, chan)
+        if mlp.scale_featurization:
+            feat = torch.cat([feat, scale_features(mlp, posts, rays, flip, spin, S, model.std_scale)], dim=-1)
         glo = None if (is_prop or glo_vec is None) else mlp.glo_affine(glo_vec.reshape(N, -1))
         density, rgbs = field_heads(mlp, feat, vd, N, S, chan, glo)
         if getattr(cfg, 'brightness_correction', False):              # models.py:233-235 (gated on this flag)
