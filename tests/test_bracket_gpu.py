@@ -28,7 +28,7 @@ K = 2.0
 # Deliberate trades, each named in DESIGN.md "Parity analysis" with its measured ratio e_hip / e_ref; the bar is 1.5 x the largest
 # ratio measured (margin for seed-to-seed spread):
 #   * the contracted std feeds only the erf damping and is formed with exp2(log2(.) / 3) on the fast transcendental units
-#     instead of powf (csrc/march_features.hip): largest ratio RATIO_CSTD on the four cast patterns;
+#     instead of powf (csrc/grid_cast.h): largest ratio RATIO_CSTD on the four cast patterns;
 #   * UCN_BWD_FIXED_POINT (the autocast training step's table-gradient mode; the float32 step keeps exact float adds) rounds
 #     every addend to a 2^-29-class grid of its task's summed |gradient|.  With a random upstream gradient that is an ADDITIVE
 #     floor of 6e-6 - 9e-5 (config B) / 1.3e-5 - 8e-4 (waymo.gin grid) in a level's relative L2, far above the float32

@@ -316,7 +316,7 @@ def test_bench_two_ranks_flow_on_one_gpu():
 
 def test_backward_of_a_grid_with_more_than_32_row_blocks_per_level():
     """The reference's own waymo.gin grid (L = 10, C = 4, T = 2^21: 256 row blocks of 8192 rows per hashed level) goes through the
-    row-block kernel as well (multi-word sample masks, march_features.hip `coarse == 3`): same table gradient as the global-atomic
+    row-block kernel as well (multi-word sample masks, march_features_bwd.hip `coarse == 3`): same table gradient as the global-atomic
     kernel (other summation order), and the exact adjoint of the forward, level by level."""
     from ucnerf_amd import _lib
     lib = _lib.load()

@@ -1,5 +1,5 @@
 // Microbenchmark: LDS ds_add_f32 cost model on one 128 KiB accumulator block per workgroup (the row-block
-// backward of march_features.hip).  hipcc --offload-arch=gfx950 -O3 tools/lds_atomic_bench.hip -o tools/_exp/lds_atomic_bench
+// backward of the featurisation, march_features_bwd.hip).  hipcc --offload-arch=gfx950 -O3 tools/lds_atomic_bench.hip -o tools/_exp/lds_atomic_bench
 //   pattern 0: lane-consecutive words        1: random words          2: one word for the whole wave
 //   pattern 3: random, 1 lane in 4 active    4: random row, 2 channels (two ds_add per lane, like C = 2)
 //   pattern 5: like 4 but ONE 8-byte read-modify-write under "this wave owns the row" (non-atomic ceiling)

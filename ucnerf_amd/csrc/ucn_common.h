@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <type_traits>
 
 #include "../../include/ucnerf_march.h"
 
@@ -68,3 +69,16 @@ __device__ __forceinline__ uint32_t ucn_row3(const UcnLevel &lv, uint32_t side, 
 }
 
 static inline uint32_t ucn_div_up(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
+
+// Host: the run-time level width C in {1, 2, 4, 8} (GridEncoding's level_dim) as a compile-time constant:
+//     ucn_for_level_dim(lv.C, [&](auto cc) { constexpr uint32_t CC = decltype(cc)::value; launch k<CC> ... });
+// Any other C calls nothing (ucn_build_levels / the entry points have refused it before).
+template <typename Fn>
+static inline void ucn_for_level_dim(uint32_t C, Fn &&fn) {
+    switch (C) {
+        case 1: fn(std::integral_constant<uint32_t, 1>{}); break;
+        case 2: fn(std::integral_constant<uint32_t, 2>{}); break;
+        case 4: fn(std::integral_constant<uint32_t, 4>{}); break;
+        case 8: fn(std::integral_constant<uint32_t, 8>{}); break;
+    }
+}
