@@ -12,15 +12,15 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # UCN_LIB_PATH: another build of the same ABI for A/B measurements; default = the in-tree product
 LIB_PATH = os.environ.get("UCN_LIB_PATH") or os.path.join(_HERE, "csrc", "libucnerf_march.so")
 ABI_VERSION = 28
-LAUNCH_CORESIDENT = 0x100
+LAUNCH_CORESIDENT = 0x100  # include/ucnerf_march.h UCN_LAUNCH_CORESIDENT
 TABLE_F16 = 0x200
 RAYS_INCOHERENT = 0x1000   # ucn_march_features layout flag: random (training) rays -> lane-paired fetch on every hashed level
-GFEAT_LEVEL_MAJOR4 = 0x20000  # ... for level_dim 4: [F / 4][M][4], / 6
 GFEAT_LEVEL_MAJOR = 0x10000  # ucn_train_bwd F flag: gfeat as [F / 2][M][2], / 6 = ucn_march_features_backward's layout 4 (include/ucnerf_march.h)
+GFEAT_LEVEL_MAJOR4 = 0x20000  # ... for level_dim 4: [F / 4][M][4], / 6
 BWD_FIXED_POINT = 0x800    # ucn_march_features_backward layout flag: int32 fixed-point row blocks (include/ucnerf_march.h UCN_BWD_FIXED_POINT)
 FEATURES_BF16 = 0x400      # ucn_march_features layout flag: features as [L][B] bf16 pairs (half tables, level_dim 2)
+FEAT_BF16 = 0x100          # ucn_train_fwd feat_level_dim flag: the features are those pairs
 LEVEL_SCALE_WS_FLOATS = 24 * 64  # include/ucnerf_march.h UCN_LEVEL_SCALE_WS_FLOATS
-FEAT_BF16 = 0x100          # ucn_train_fwd feat_level_dim flag: the features are those pairs          # include/ucnerf_march.h UCN_LAUNCH_CORESIDENT
 
 c_u32, c_u64, c_i32, c_f32, c_vp = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int, ctypes.c_float, ctypes.c_void_p
 

@@ -234,6 +234,21 @@ def gemm(x, w, bias=None, flags=0, out=None, n_out=None, mask=None, rowbias=None
 _WS = {}
 
 
+def stream_workspace(n_floats, device, kernel="f32"):
+    """A split-K workspace of >= n_floats per weight-gradient kernel ("f32" here, "bf16": heads_bf16.wgrad), device and stream (the sky
+    branch runs beside the field), keyed by the Stream OBJECT kept alive in the entry: a raw handle value can be recycled by a later
+    stream and would alias a workspace still in flight."""
+    cache = _WS.setdefault(kernel, {})
+    st = torch.cuda.current_stream()
+    key = (str(device), st.cuda_stream)
+    hit = cache.get(key)
+    if hit is None or hit[0] != st or hit[1].numel() < n_floats:
+        if len(cache) > 8:
+            cache.clear()
+        hit = cache[key] = (st, torch.empty(max(n_floats, 1), device=device))
+    return hit[1]
+
+
 def wgrad(gy, x, want_bias=False):
     """(gy^T x as [N, K] float32, column sums of gy [N] or None); gy [M, N], x [M, K] as returned by _rows."""
     lib = _lib.load()
@@ -245,20 +260,14 @@ def wgrad(gy, x, want_bias=False):
         return wgrad(x, gy, False)[0].t().contiguous(), None
     split = _ENGINE == "split" and M >= H3_MIN_ROWS
     n = (lib.ucn_wgrad_h3_ws_floats if split else lib.ucn_wgrad_f32_ws_floats)(N, K, M)
-    st = torch.cuda.current_stream()
-    key = (str(gy.device), st.cuda_stream)
-    hit = _WS.get(key)
-    if hit is None or hit[0] != st or hit[1].numel() < n:
-        if len(_WS) > 8:
-            _WS.clear()
-        hit = _WS[key] = (st, torch.empty(max(n, 1), device=gy.device))
+    ws = stream_workspace(n, gy.device)
     gw = torch.empty(N, K, device=gy.device)
     gb = torch.empty(N, device=gy.device) if want_bias else None
     if split:
         _lib.check(lib.ucn_wgrad_h3(gy.data_ptr(), gy.stride(0), x.data_ptr(), x.stride(0), amax_of(gy).data_ptr(), amax_of(x).data_ptr(),
-                                    M, N, K, hit[1].data_ptr(), gw.data_ptr(), _lib.ptr(gb), _lib.stream()))
+                                    M, N, K, ws.data_ptr(), gw.data_ptr(), _lib.ptr(gb), _lib.stream()))
         return gw, gb
-    _lib.check(lib.ucn_wgrad_f32(gy.data_ptr(), gy.stride(0), x.data_ptr(), x.stride(0), M, N, K, hit[1].data_ptr(), gw.data_ptr(),
+    _lib.check(lib.ucn_wgrad_f32(gy.data_ptr(), gy.stride(0), x.data_ptr(), x.stride(0), M, N, K, ws.data_ptr(), gw.data_ptr(),
                                  _lib.ptr(gb), _lib.stream()))
     return gw, gb
 
@@ -307,6 +316,10 @@ def hip_linear(x, weight, bias=None, relu=False):
     return _HipLinear.apply(x, weight, bias, relu)
 
 
+def device_f32(*tensors):
+    return all(t is None or (t.is_cuda and t.dtype == torch.float32) for t in tensors)
+
+
 def usable(*tensors):
     """the fp32 route's kernels take float32 device tensors outside autocast"""
-    return (not torch.is_autocast_enabled()) and all(t is None or (t.is_cuda and t.dtype == torch.float32) for t in tensors)
+    return (not torch.is_autocast_enabled()) and device_f32(*tensors)

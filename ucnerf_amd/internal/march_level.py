@@ -1,5 +1,5 @@
 """What a sampling level needs around its kernels, once for both marches (ref models.py:97-324): `Model._march` (models.py, the
-fused inference march) and `march_train` (train_graph.py, the autograd march) walk the same level schedule.  Here: the batch's
+fused inference march) and `march_train` (train_graph.py, the autograd march; its nodes: march_nodes.py) walk the same level schedule.  Here: the batch's
 rays, the level plan and anneal value, the random draws in the reference's order, a level's fenceposts with the choice between
 an entry point and its `_tdist` sibling, and the result dictionaries.  What runs in between -- featurisation, dense layers,
 compositing, the sky and brightness tails -- stays with each march (kernels in one, autograd nodes in the other)."""

@@ -14,7 +14,7 @@ ray-distance curve of coord.construct_ray_warps (raydist_fn None, 'piecewise', '
 torch.reciprocal / log / exp / sqrt / square; DESIGN.md "Ray-distance curves") and the featurized grid scale
 (MLP.scale_featurization).  Anything else raises at construction.
 In eval mode or with gradients disabled forward is the fused inference march; a model in training mode
-with gradients enabled routes to internal/train_graph.py (same kernels for resampling and featurisation, HIP
+with gradients enabled routes to internal/train_graph.py `march_train` (same kernels for resampling and featurisation, HIP
 backward for the tables and the dense layers' dgrad, autograd glue; `Model.march_route`).  Without the HIP library or a GPU every entry point raises.
 """
 import ctypes
@@ -26,6 +26,7 @@ import torch.nn as nn
 from .. import _lib
 from ..gridencoder import GridEncoder
 from . import march_level as ml
+from .head_pack import prepare_heads, rgb_activation, view_encoding
 from .extrinsic_optimizer import BrightnessCorrection
 from .march_level import _f32, _u_table  # noqa: F401  (_u_table: not used here, kept importable for tests and tools)
 from .sky import NeRF, render_rays  # noqa: F401  (names kept importable like upstream)
@@ -343,6 +344,14 @@ class MLP(nn.Module):
             self._grid_desc, self._grid_desc_key = d, key
         return self._grid_desc
 
+    def grid_field_with(self, embeddings):
+        """A copy of `grid_field()` that reads another table of the same layout: the half-precision copy of an autocast pass
+        (gridencoder/grid.py:41-44).  The caller keeps `embeddings` alive for as long as it uses the descriptor."""
+        d = _lib.UcnField()
+        ctypes.memmove(ctypes.byref(d), ctypes.byref(self.grid_field()), ctypes.sizeof(_lib.UcnField))
+        d.embeddings = embeddings.data_ptr()
+        return d
+
     # ---- reference API on explicit Gaussians (extract.py:56-57,96) ---------------------------
     @torch.no_grad()
     def predict_density(self, means, stds, rand=False, no_warp=False):
@@ -366,7 +375,7 @@ class MLP(nn.Module):
                     normals_pred=None, roughness=None)
 
     def _forward_glo(self, means, stds, viewdirs, glo_vec, no_warp):
-        from . import train_graph as tg
+        from .heads_f32 import _ColourMLPGlo
         raw, x, coord = self.predict_density(means, stds, no_warp=no_warp)
         prefix = raw.shape
         vd = _f32(viewdirs, -1, 3)
@@ -378,10 +387,10 @@ class MLP(nn.Module):
         with torch.autocast('cuda', enabled=False):
             a, b = self.glo_affine(glo_vec.reshape(N, -1).float())
             l0, l1 = self.lin_second_stage_0, self.lin_second_stage_1
-            h, _ = tg._ColourMLPGlo.apply(x.reshape(B, -1), a, b, tg.view_encoding(vd, self.deg_view), l0.weight, l0.bias,
-                                          l1.weight, l1.bias, N, B // N)
+            h, _ = _ColourMLPGlo.apply(x.reshape(B, -1), a, b, view_encoding(vd, self.deg_view), l0.weight, l0.bias,
+                                       l1.weight, l1.bias, N, B // N)
             logits = torch.nn.functional.linear(h, self.rgb_layer.weight, self.rgb_layer.bias)
-        rgb = torch.sigmoid(self.rgb_premultiplier * logits + self.rgb_bias) * (1 + 2 * self.rgb_padding) - self.rgb_padding
+        rgb = rgb_activation(self, logits)
         return dict(coord=coord, density=density, rgb=rgb.reshape(prefix + (3,)), raw_grad_density=None, grad_pred=None,
                     normals=None, normals_pred=None, roughness=None)
 
@@ -593,13 +602,10 @@ class Model(nn.Module):
             return None
         if mlp.scale_featurization:                # the bf16 inference kernels read grid planes only: fp32-class path
             return None
-        from . import train_graph as tg
+        from .train_graph import heads_route
         emb = mlp.encoder.embeddings
-        probe = torch.empty(1, F_in, device=emb.device)
-        if is_prop:
-            if not tg._fusable_prop(mlp, probe):
-                return None
-        elif not tg._fusable_heads(mlp, probe):
+        # the level's bf16 kernels are the training step's: the same route decision (no GLO here: every inference march is zero_glo)
+        if heads_route(mlp, F_in, emb.is_cuda, torch.bfloat16, None) != ("prop_fused" if is_prop else "fused_bf16"):      # (the features are fp32)
             return None
         # the half table and the packed weights are rebuilt only when a parameter changed (a frame is tens of chunks)
         key = tuple((p.data_ptr(), p._version) for p in mlp.parameters()) + (bool(self.autocast_bf16_features),)
@@ -609,12 +615,9 @@ class Model(nn.Module):
             return hit[1]
         out = {}
         half = mlp.encoder.level_dim % 2 == 0                      # grid.py:41-44: half tables when C is even
-        d16 = _lib.UcnField()
-        ctypes.memmove(ctypes.byref(d16), ctypes.byref(mlp.grid_field()), ctypes.sizeof(_lib.UcnField))
         if half:
             out['table'] = emb.detach().to(torch.half)
-            d16.embeddings = out['table'].data_ptr()
-        out['desc'], out['table_flag'] = d16, (_lib.TABLE_F16 if half else 0)
+        out['desc'], out['table_flag'] = mlp.grid_field_with(out['table'] if half else emb), (_lib.TABLE_F16 if half else 0)
         # the NeRF level's features leave the gather as the bf16 pairs its MLP consumes (half the workspace traffic)
         out['feat_flag'] = _lib.FEATURES_BF16 if (half and mlp.encoder.level_dim == 2 and not is_prop and self.autocast_bf16_features) else 0
         with torch.autocast('cuda', enabled=False):
@@ -625,12 +628,12 @@ class Model(nn.Module):
                 d0, d1, c0, c1, lr = mlp.density_layer[0], mlp.density_layer[2], mlp.lin_second_stage_0, mlp.lin_second_stage_1, mlp.rgb_layer
                 # a GLO field: the zero code's modulation folded into the colour layers (every inference march here is zero_glo)
                 W0, b0, W1, b1 = mlp._glo_folded() if mlp.uses_glo() else (c0.weight, c0.bias, c1.weight, c1.bias)
-                packed, _, We, be, bias0, bias1, biasr = tg.prepare_heads(d0.weight, d0.bias, d1.weight, d1.bias, W0, b0,
-                                                                         W1, b1, lr.weight, lr.bias, dir_in_stream=True)
+                packed, _, We, be, bias0, bias1, biasr = prepare_heads(d0.weight, d0.bias, d1.weight, d1.bias, W0, b0,
+                                                                      W1, b1, lr.weight, lr.bias, dir_in_stream=True)
                 out.update(packed=packed, We=We, be=be, bias0=bias0, bias1=bias1, biasr=biasr, NW=c0.weight.shape[0],
                            head=(ctypes.c_float * 4)(float(mlp.density_bias), float(mlp.rgb_premultiplier), float(mlp.rgb_bias),
                                                      float(mlp.rgb_padding)),
-                           enc=lambda v: _dir_tiles(tg.view_encoding(v.float(), mlp.deg_view)))
+                           enc=lambda v: _dir_tiles(view_encoding(v.float(), mlp.deg_view)))
         cache[id(mlp)] = (key, out)
         return out
 
@@ -881,7 +884,7 @@ def unwrap_model(model):
 
 def _dir_tiles(enc):
     """[N, E <= 31] direction encodings -> [N, 32] bf16 tiles [enc, 1, 0...]: the input tile whose column E meets the bias column
-    of the colour layers' weight streams (train_graph._head_gather_index(dir_in_stream=True))."""
+    of the colour layers' weight streams (head_pack._head_gather_index(dir_in_stream=True))."""
     n, e = enc.shape
     t = torch.zeros(n, 32, device=enc.device, dtype=torch.bfloat16)
     t[:, :e] = enc
