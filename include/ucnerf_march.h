@@ -290,6 +290,29 @@ int ucn_march_scale_features_tdist(const ucn_field_t *f, const float *tdist, con
 int ucn_points_scale_features(const ucn_field_t *f, const float *means, const float *stds, uint32_t B, uint32_t G, int warp,
                               const float *level_scale, int sample_major, float *scale_out, ucn_stream_t stream);
 
+/* ------------------------------------------------- density normals (ABI 29; ref: models.py:546-567, MLP.disable_density_normals = False)
+ * raw_grad_density = mean over a sample's multisamples j of d raw_density / d x_j (x_j the world-space mean before the warp,
+ * std_j held constant), normals = -raw_grad_density / max(|raw_grad_density|, float32 eps).  The gradient runs through the grid
+ * interpolation (d feat / d u with the level's scale as in gridencoder.cu's dy_dx, the erf damping, 1/G, the contraction's
+ * Jacobian / 4) and through the erf damping (the contraction scales std by det_13(|x|) outside the unit ball).  Two calls, after
+ * the level's ucn_field_mlp, on the same stream:
+ *
+ * ucn_density_feature_grad: gfeat[l][b][c] = d raw_density / d features[l][b][c] = (W0^T (1[h > 0] * W1[0, :]))[l*C + c] with
+ * h = W0 features + b0 recomputed in fp32 from w_d0 / b_d0 / w_d1 (the unpacked weights) in every mlp_mode.  features and
+ * gfeat_out are [num_levels][B][level_dim]; gfeat_out may BE features (in place).  A field with n_scale_planes > 0 is refused. */
+int ucn_density_feature_grad(const ucn_field_t *f, const float *features, uint32_t B, float *gfeat_out, ucn_stream_t stream);
+/* The samples ucn_march_features featurises (same ray arguments, same Gaussians bit for bit).  fenceposts: sdist [N,S+1] read
+ * with near_ / far_, or -- near_ = far_ = NULL -- metric tdist (ucn_s_to_t); bit-identical on the identity curve's tdist.
+ * layout 0 / 2: gfeat is [L][N*S][C] with b = ray*S + s / b = s*N + ray, as ucn_march_features wrote the features.
+ * raw_grad_out, normals_out: [N,S,3], always [ray][s].  f: the grid part only.  No atomics, no workspace. */
+int ucn_march_density_grad(const ucn_field_t *f, const float *fenceposts, const float *near_, const float *far_,
+                           const float *origins, const float *directions, const float *basis, const float *radii,
+                           const float *flip, const float *spin, float std_scale, uint32_t N, uint32_t S, int layout,
+                           const float *gfeat, float *raw_grad_out, float *normals_out, ucn_stream_t stream);
+/* ... for caller-supplied Gaussians, beside ucn_points_features: means [B,G,3], stds [B,G], gfeat [L][B][C] -> [B,3] each. */
+int ucn_points_density_grad(const ucn_field_t *f, const float *means, const float *stds, uint32_t B, uint32_t G, int warp,
+                            const float *gfeat, float *raw_grad_out, float *normals_out, ucn_stream_t stream);
+
 /* ref: coord.py:214-225 pos_enc(viewdirs): the per-ray direction inputs of the colour MLP.
  * mlp_mode 0: folded through the direction columns of lin_second_stage_{0,1} into additive terms
  *             [N,2,n_width];  mlp_mode 1: the encoding itself as one 32-wide input tile [N,32]

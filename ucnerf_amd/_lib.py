@@ -11,7 +11,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # UCN_LIB_PATH: another build of the same ABI for A/B measurements; default = the in-tree product
 LIB_PATH = os.environ.get("UCN_LIB_PATH") or os.path.join(_HERE, "csrc", "libucnerf_march.so")
-ABI_VERSION = 28
+ABI_VERSION = 29
 LAUNCH_CORESIDENT = 0x100  # include/ucnerf_march.h UCN_LAUNCH_CORESIDENT
 TABLE_F16 = 0x200
 RAYS_INCOHERENT = 0x1000   # ucn_march_features layout flag: random (training) rays -> lane-paired fetch on every hashed level
@@ -96,6 +96,10 @@ SIGNATURES = {
     "ucn_march_scale_features_tdist": [ctypes.POINTER(UcnField), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_u32, c_u32, c_vp,
                                        c_i32, c_vp, c_vp],
     "ucn_points_scale_features": [ctypes.POINTER(UcnField), c_vp, c_vp, c_u32, c_u32, c_i32, c_vp, c_i32, c_vp, c_vp],
+    "ucn_density_feature_grad": [ctypes.POINTER(UcnField), c_vp, c_u32, c_vp, c_vp],
+    "ucn_march_density_grad": [ctypes.POINTER(UcnField), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_u32, c_u32, c_i32,
+                               c_vp, c_vp, c_vp, c_vp],
+    "ucn_points_density_grad": [ctypes.POINTER(UcnField), c_vp, c_vp, c_u32, c_u32, c_i32, c_vp, c_vp, c_vp, c_vp],
     "ucn_field_dir_floats": [ctypes.POINTER(UcnField), c_u32],
     "ucn_field_dir_bias": [ctypes.POINTER(UcnField), c_vp, c_u32, c_vp, c_vp],
     "ucn_field_mlp": [ctypes.POINTER(UcnField), c_vp, c_u32, c_u32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp],

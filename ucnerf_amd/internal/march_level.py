@@ -3,6 +3,7 @@ fused inference march) and `march_train` (train_graph.py, the autograd march; it
 rays, the level plan and anneal value, the random draws in the reference's order, a level's fenceposts with the choice between
 an entry point and its `_tdist` sibling, and the result dictionaries.  What runs in between -- featurisation, dense layers,
 compositing, the sky and brightness tails -- stays with each march (kernels in one, autograd nodes in the other)."""
+import ctypes
 import functools
 
 import numpy as np
@@ -120,6 +121,11 @@ class Fenceposts:
         return [t[sl].data_ptr() for t in fence + (rays.o, rays.d, self.basis, rays.rad)] + [
             None if flip is None else flip[sl].data_ptr(), None if spin is None else spin[sl].data_ptr()]
 
+    def normals_geometry(self, rays, flip, spin, sl=slice(None)):
+        """`geometry` for ucn_march_density_grad, which has no `_tdist` sibling: metric fenceposts go with near = far = NULL."""
+        g = self.geometry(rays, flip, spin, sl)
+        return g if self.tdist is None else [g[0], None, None] + g[1:]
+
     def compositing(self, sl=slice(None), backward=False):
         """The compositing arguments for the rays `sl`; the forward `_tdist` sibling also reads the batch's metric far."""
         fence = (self.sdist, self.near, self.far) if self.tdist is None else (self.tdist,) if backward else (self.tdist, self.far)
@@ -146,12 +152,26 @@ def fenceposts(model, rays, i_level, S, dilation, train_frac, rand, prev, weight
     return Fenceposts(sdist, rays.near, rays.far, s_to_t(model, sdist, rays.near, rays.far, stream), basis), flip, spin
 
 
+def density_normals(mlp, posts, rays, flip, spin, sl, n, S, std_scale, layout, feat, raw_grad, normals, stream, field=None):
+    """models.py:550-567 for the n rays `sl` of a level, after its dense layers, on `stream`: the feature buffer `feat` ([L][n*S][C],
+    layout 0 or 2 as ucn_march_features wrote it) becomes d raw_density / d features IN PLACE (ucn_density_feature_grad), then the second
+    gather fills raw_grad[sl] and normals[sl] ([N, S, 3]).  Nothing here carries an autograd graph.  field: the level's
+    mlp.normals_field(), for a caller that runs many passes of one level."""
+    lib = _lib.load()
+    d = mlp.normals_field() if field is None else field
+    _lib.check(lib.ucn_density_feature_grad(ctypes.byref(d), feat.data_ptr(), n * S, feat.data_ptr(), stream))
+    _lib.check(lib.ucn_march_density_grad(ctypes.byref(d), *posts.normals_geometry(rays, flip, spin, sl), float(std_scale), n, S, layout,
+                                          feat.data_ptr(), raw_grad[sl].data_ptr(), normals[sl].data_ptr(), stream))
+
+
 # ---- result dictionaries (the keys of ref models.py:262-324) -------------------------------------------------------------
-def rendering_entry(rgb, depth, acc, weights, extras, prefix, sdist=None, rgbs=None, n_vis=16):
+def rendering_entry(rgb, depth, acc, weights, extras, prefix, sdist=None, rgbs=None, n_vis=16, normals=None):
     """rgb [N, 3], depth [N], acc [N], weights [N, S]; with extras [N, 4] (compute_extras: distance mean, 5 %, median, 95 %) also the
     'ray_*' keys: the first n_vis rays' fenceposts, weights and colours (rgbs None, a proposal level: zeros until `broadcast_final`)."""
     N, S = weights.shape
     r = dict(rgb=rgb.reshape(prefix + (3,)), depth=depth.reshape(prefix), acc=acc.reshape(prefix))
+    if extras is not None and normals is not None:          # render.py:218-222: alpha-composited like the colours, no background term
+        r['normals'] = (weights.detach()[..., None] * normals).sum(dim=-2).reshape(prefix + (3,))
     if extras is not None:
         for j, k in enumerate(('distance_mean', 'distance_percentile_5', 'distance_median', 'distance_percentile_95')):
             r[k] = extras[:, j].reshape(prefix)
@@ -169,10 +189,11 @@ def broadcast_final(renderings):
         r['ray_rgbs'] = final[:, None, :].expand(r['ray_rgbs'].shape)
 
 
-def history_entry(coord, density, rgbs, sdist, weights, prefix):
+def history_entry(coord, density, rgbs, sdist, weights, prefix, raw_grad=None, normals=None):
     """coord [N, S, 3], density [N, S], rgbs [N, S, 3] or None (zeros), sdist [N, S+1], weights [N, S]."""
     N, S = weights.shape
     rgb = torch.zeros(N, S, 3, device=weights.device) if rgbs is None else rgbs
     return dict(coord=coord.reshape(prefix + (S, 3)), density=density.reshape(prefix + (S,)), rgb=rgb.reshape(prefix + (S, 3)),
-                raw_grad_density=None, grad_pred=None, normals=None, normals_pred=None, roughness=None,
+                raw_grad_density=None if raw_grad is None else raw_grad.reshape(prefix + (S, 3)), grad_pred=None,
+                normals=None if normals is None else normals.reshape(prefix + (S, 3)), normals_pred=None, roughness=None,
                 sdist=sdist.reshape(prefix + (S + 1,)).clone(), weights=weights.reshape(prefix + (S,)).clone())

@@ -12,7 +12,8 @@ Supported configuration = the reference's shipped one (configs/waymo.gin): disab
 no reflections / diffuse / IDE, plus GLO appearance codes (num_glo_features > 0; DESIGN.md "GLO") and every
 ray-distance curve of coord.construct_ray_warps (raydist_fn None, 'piecewise', 'power_transformation' or a gin-bound
 torch.reciprocal / log / exp / sqrt / square; DESIGN.md "Ray-distance curves") and the featurized grid scale
-(MLP.scale_featurization).  Anything else raises at construction.
+(MLP.scale_featurization) and analytic density normals (MLP.disable_density_normals = False).
+Anything else raises at construction.
 In eval mode or with gradients disabled forward is the fused inference march; a model in training mode
 with gradients enabled routes to internal/train_graph.py `march_train` (same kernels for resampling and featurisation, HIP
 backward for the tables and the dense layers' dgrad, autograd glue; `Model.march_route`).  Without the HIP library or a GPU every entry point raises.
@@ -149,7 +150,7 @@ class MLP(nn.Module):
         set_kwargs(self, kwargs)
         unsupported = dict(use_reflections=False, use_directional_enc=False, enable_pred_roughness=False,
                            use_diffuse_color=False, use_specular_tint=False, use_n_dot_v=False,
-                           enable_pred_normals=False, disable_density_normals=True,
+                           enable_pred_normals=False,
                            net_depth_viewdirs=2, skip_layer_dir=0, num_rgb_channels=3,
                            warp_fn='contract', bottleneck_noise=0.0, density_noise=0.0)
         for k, want in unsupported.items():
@@ -157,6 +158,11 @@ class MLP(nn.Module):
                 raise NotImplementedError(
                     f"{type(self).__name__}.{k}={getattr(self, k)!r}: the HIP ray-march implements the shipped "
                     f"waymo.gin configuration only ({k}={want!r})")
+        if not self.disable_density_normals and self.scale_featurization:
+            raise NotImplementedError(
+                f"{type(self).__name__}: disable_density_normals=False with scale_featurization=True: the density gradient's term "
+                "through the scale features (their erf damping depends on the position outside the unit ball) is not built "
+                "(DESIGN.md 7d)")
         self.grid_num_levels = int(np.log(self.grid_disired_resolution / self.grid_base_resolution)
                                    / np.log(self.grid_level_interval)) + 1
         self.encoder = GridEncoder(input_dim=3, num_levels=self.grid_num_levels, level_dim=self.grid_level_dim,
@@ -344,6 +350,20 @@ class MLP(nn.Module):
             self._grid_desc, self._grid_desc_key = d, key
         return self._grid_desc
 
+    def normals_field(self):
+        """A copy of `grid_field()` with the unpacked density_layer pointers: what the density-normal kernels read
+        (ucn_density_feature_grad recomputes the hidden layer in fp32 from them).  No packed stream: the training
+        route uses it every step.  The caller keeps it alive for the launches it makes with it."""
+        d = _lib.UcnField()
+        ctypes.memmove(ctypes.byref(d), ctypes.byref(self.grid_field()), ctypes.sizeof(_lib.UcnField))
+        ws = [self.density_layer[0].weight, self.density_layer[0].bias, self.density_layer[2].weight, self.density_layer[2].bias]
+        for w in ws:
+            _lib.require_device(w, f"{type(self).__name__} parameter")
+            if w.dtype != torch.float32 or not w.is_contiguous():
+                raise RuntimeError("field parameters must be contiguous float32")
+        d.w_d0, d.b_d0, d.w_d1, d.b_d1 = (w.data_ptr() for w in ws)
+        return d
+
     def grid_field_with(self, embeddings):
         """A copy of `grid_field()` that reads another table of the same layout: the half-precision copy of an autocast pass
         (gridencoder/grid.py:41-44).  The caller keeps `embeddings` alive for as long as it uses the descriptor."""
@@ -357,7 +377,7 @@ class MLP(nn.Module):
     def predict_density(self, means, stds, rand=False, no_warp=False):
         """ref models.py:485-512.  means [..., G, 3], stds [..., G] -> (raw_density [...],
         x [..., n_out], mean contracted coordinate [..., 3])."""
-        raw, x, coord, _, _ = self._evaluate(means, stds, None, no_warp, want_x=True)
+        raw, x, coord, _, _, _ = self._evaluate(means, stds, None, no_warp, want_x=True, want_normals=False)
         return raw, x, coord
 
     @torch.no_grad()
@@ -368,15 +388,15 @@ class MLP(nn.Module):
         node (_ColourMLPGlo) on the fp32 kernel's bottleneck, without gradients."""
         if glo_vec is not None and self.uses_glo() and viewdirs is not None:
             return self._forward_glo(means, stds, viewdirs, glo_vec, no_warp)
-        _, _, coord, density, rgb = self._evaluate(means, stds, viewdirs, no_warp, want_x=False)
+        _, _, coord, density, rgb, (raw_grad, normals) = self._evaluate(means, stds, viewdirs, no_warp, want_x=False)
         if self.disable_rgb or viewdirs is None:
             rgb = torch.zeros(density.shape + (3,), device=density.device)
-        return dict(coord=coord, density=density, rgb=rgb, raw_grad_density=None, grad_pred=None, normals=None,
+        return dict(coord=coord, density=density, rgb=rgb, raw_grad_density=raw_grad, grad_pred=None, normals=normals,
                     normals_pred=None, roughness=None)
 
     def _forward_glo(self, means, stds, viewdirs, glo_vec, no_warp):
         from .heads_f32 import _ColourMLPGlo
-        raw, x, coord = self.predict_density(means, stds, no_warp=no_warp)
+        raw, x, coord, _, _, (raw_grad, normals) = self._evaluate(means, stds, None, no_warp, want_x=True)
         prefix = raw.shape
         vd = _f32(viewdirs, -1, 3)
         N = vd.shape[0]
@@ -391,10 +411,10 @@ class MLP(nn.Module):
                                        l1.weight, l1.bias, N, B // N)
             logits = torch.nn.functional.linear(h, self.rgb_layer.weight, self.rgb_layer.bias)
         rgb = rgb_activation(self, logits)
-        return dict(coord=coord, density=density, rgb=rgb.reshape(prefix + (3,)), raw_grad_density=None, grad_pred=None,
-                    normals=None, normals_pred=None, roughness=None)
+        return dict(coord=coord, density=density, rgb=rgb.reshape(prefix + (3,)), raw_grad_density=raw_grad, grad_pred=None,
+                    normals=normals, normals_pred=None, roughness=None)
 
-    def _evaluate(self, means, stds, viewdirs, no_warp, want_x):
+    def _evaluate(self, means, stds, viewdirs, no_warp, want_x, want_normals=True):
         # the split-f16 kernel composes the bottleneck away; the API that returns it uses the fp32 kernel's packed copy
         mode = 0 if (want_x and not self.disable_rgb) else int(self.mlp_mode)
         lib = _lib.load()
@@ -435,6 +455,15 @@ class MLP(nn.Module):
             rgb = torch.empty(B, 3, device=dev)
         _lib.check(lib.ucn_field_mlp(ctypes.byref(d), feat.data_ptr(), B, spr, 0, _lib.ptr(dirb), density.data_ptr(),
                                      _lib.ptr(rgb), _lib.ptr(x), st))
+        nrm = (None, None)
+        if want_normals and not self.disable_density_normals:
+            # models.py:550-567: after the field MLP, on the same stream; the feature buffer is free and becomes gfeat in place
+            nd = self.normals_field()
+            raw_grad, normals = torch.empty(B, 3, device=dev), torch.empty(B, 3, device=dev)
+            _lib.check(lib.ucn_density_feature_grad(ctypes.byref(nd), feat.data_ptr(), B, feat.data_ptr(), st))
+            _lib.check(lib.ucn_points_density_grad(ctypes.byref(nd), m.data_ptr(), s.data_ptr(), B, G, 0 if no_warp else 1,
+                                                   feat.data_ptr(), raw_grad.data_ptr(), normals.data_ptr(), st))
+            nrm = (raw_grad.reshape(prefix + (3,)), normals.reshape(prefix + (3,)))
         # raw (pre-activation) density: softplus is inverted only for API parity of predict_density
         raw = None
         if want_x:
@@ -443,7 +472,7 @@ class MLP(nn.Module):
             raw = x[:, 0].reshape(prefix)
             x = x.reshape(prefix + (n_out,))
         return (raw, x, coord.reshape(prefix + (3,)), density.reshape(prefix),
-                None if rgb is None else rgb.reshape(prefix + (3,)))
+                None if rgb is None else rgb.reshape(prefix + (3,)), nrm)
 
 
 @_configurable
@@ -536,6 +565,12 @@ class Model(nn.Module):
                 raise NotImplementedError(f"Model.{k}={getattr(self, k)!r} is outside the shipped waymo.gin path")
         if self.bg_intensity_range[0] != self.bg_intensity_range[1]:
             raise NotImplementedError("random background colours (bg_intensity_range) are not on the shipped path")
+        for k in ('orientation_loss_mult', 'predicted_normal_loss_mult'):
+            # the only consumers of the normals' own gradient (the reference's create_graph=True, models.py:559): not built,
+            # the normals are returned detached; both default to 0 (configs.py:81,85)
+            if getattr(config, k, 0):
+                raise NotImplementedError(f"config.{k}={getattr(config, k)!r}: the second-order path through the density normals "
+                                          "is not built (normals are returned detached)")
         self.nerf_mlp = NerfMLP(num_glo_features=self.num_glo_features, num_glo_embeddings=self.num_glo_embeddings)
         for i in range(self.num_levels - 1):
             self.register_module(f'prop_mlp_{i}', PropMLP(grid_disired_resolution=self.prop_desired_grid_size[i]))
@@ -601,6 +636,8 @@ class Model(nn.Module):
         if not (self.autocast_render and torch.is_autocast_enabled() and torch.get_autocast_dtype('cuda') == torch.bfloat16):
             return None
         if mlp.scale_featurization:                # the bf16 inference kernels read grid planes only: fp32-class path
+            return None
+        if not mlp.disable_density_normals:        # the normals pass reads fp32 features of the fp32 table: fp32-class path
             return None
         from .train_graph import heads_route
         emb = mlp.encoder.embeddings
@@ -721,6 +758,11 @@ class Model(nn.Module):
             main = torch.empty(N, 5, device=dev)
             extras = torch.empty(N, 4, device=dev) if compute_extras else None
             coord = torch.empty(N, S, 3, device=dev) if want_history else None
+            # density normals: for every sample (compacted or not), when something returns them
+            want_normals = (not mlp.disable_density_normals) and (want_history or compute_extras)
+            raw_grad = torch.empty(N, S, 3, device=dev) if want_normals else None
+            normals = torch.empty(N, S, 3, device=dev) if want_normals else None
+            normals_field = mlp.normals_field() if want_normals else None          # once per level, not per pass
             nc = min(chunk, N)
             feat = torch.empty(planes(mlp) * nc * S * C, device=dev)
             level_scale = mlp.level_scale() if mlp.scale_featurization else None
@@ -777,6 +819,10 @@ class Model(nn.Module):
                 if timed and overlap:
                     m0.record(cur)
                 run_mlp(fb, sl, r0, n)
+                if want_normals:                      # behind the MLP, on its stream: the pass's feature buffer becomes gfeat
+                    # (with _prof set, e2 below closes after it: the pass's "MLP" time then includes the normals pass)
+                    ml.density_normals(mlp, posts, rays, flip, spin, sl, n, S, self.std_scale, feat_layout & 3, fb, raw_grad, normals, st,
+                                       field=normals_field)
                 if overlap:
                     mlp_done[i_pass % 2] = torch.cuda.Event()
                     mlp_done[i_pass % 2].record(cur)
@@ -789,9 +835,10 @@ class Model(nn.Module):
                 density.data_ptr(), _lib.ptr(rgbs), *posts.compositing(), rays.d.data_ptr(),
                 float(self.bg_intensity_range[0]), int(bool(self.opaque_background)), N, S, weights.data_ptr(),
                 main.data_ptr(), _lib.ptr(extras), st))
-            renderings.append(ml.rendering_entry(main[:, 0:3], main[:, 3], main[:, 4], weights, extras, prefix, posts.sdist, rgbs, getattr(cfg, 'vis_num_rays', 16)))
+            renderings.append(ml.rendering_entry(main[:, 0:3], main[:, 3], main[:, 4], weights, extras, prefix, posts.sdist, rgbs,
+                                                 getattr(cfg, 'vis_num_rays', 16), normals=normals))
             if want_history:
-                ray_history.append(ml.history_entry(coord, density, rgbs, posts.sdist, weights, prefix))
+                ray_history.append(ml.history_entry(coord, density, rgbs, posts.sdist, weights, prefix, raw_grad, normals))
 
         if compute_extras:                                             # ref models.py:313-324
             ml.broadcast_final(renderings)

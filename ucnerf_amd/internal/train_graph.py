@@ -231,8 +231,18 @@ def march_train(model, rand, batch, train_frac, compute_extras, eval_camidx, glo
                 w_x, main_x, extras = torch.empty(N, S, device=dev), torch.empty(N, 5, device=dev), torch.empty(N, 4, device=dev)
                 _lib.check(posts.entry(lib, 'ucn_composite')(dn.data_ptr(), rg.data_ptr(), *posts.compositing(), d.data_ptr(), bg,
                                                              opaque, N, S, w_x.data_ptr(), main_x.data_ptr(), extras.data_ptr(), st))
-        renderings.append(ml.rendering_entry(c_rgb, c_depth, c_acc, weights, extras, prefix, posts.sdist, rgbs, getattr(cfg, 'vis_num_rays', 16)))
-        hist = ml.history_entry(coord, density, rgbs, posts.sdist, weights, prefix)
+        raw_grad = normals = None
+        if not mlp.disable_density_normals:
+            # models.py:550-567, detached (the second-order path of create_graph=True is not built: Model.__init__ refuses its
+            # consumers).  A level-major fp32 copy of the features becomes gfeat; the table is the fp32 one
+            with torch.no_grad():
+                L, C = mlp.encoder.num_levels, mlp.encoder.level_dim
+                gfeat = feat.detach()[:, :L * C].float().reshape(N * S, L, C).permute(1, 0, 2).contiguous()
+                raw_grad, normals = torch.empty(N, S, 3, device=dev), torch.empty(N, S, 3, device=dev)
+                ml.density_normals(mlp, posts, rays, flip, spin, slice(None), N, S, model.std_scale, 0, gfeat, raw_grad, normals, st)
+        renderings.append(ml.rendering_entry(c_rgb, c_depth, c_acc, weights, extras, prefix, posts.sdist, rgbs, getattr(cfg, 'vis_num_rays', 16),
+                                             normals=normals))
+        hist = ml.history_entry(coord, density, rgbs, posts.sdist, weights, prefix, raw_grad, normals)
         if model.training:
             hist['loss_hash_decay'] = hash_decay(mlp)
         ray_history.append(hist)
