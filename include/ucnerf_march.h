@@ -413,6 +413,12 @@ int ucn_distortion_loss(const float *t /*[N,S+1]*/, const float *w /*[N,S]*/, ui
 int ucn_interlevel_loss(const float *c, const float *w, uint32_t S_nerf, const float *cp, const float *wp,
                         uint32_t S_prop, float pulse_width, uint32_t N, float *loss_ray, float *dterm,
                         ucn_stream_t stream);
+/* ref: train_utils.py:233-244 interlevel_loss (mip-NeRF 360) for ONE proposal level (stepfun.py:6-61 lossfun_outer): same operands.
+ * cy = [0, cumsum(wp)], lo(v) = largest k with cp[k] <= v (0 if none), hi(v) = smallest k with cp[k] > v (S_prop if none),
+ * w_outer[i] = cy[hi(c[i+1])] - cy[lo(c[i])].  loss_ray [N] = sum_i max(w[i] - w_outer[i], 0)^2 / (w[i] + FLT_EPSILON); dterm [N,S_prop] =
+ * d loss_ray / d wp, a lookup into a prefix sum (no atomics: bit-identical between calls).  S_nerf <= 512, S_prop <= 1024. */
+int ucn_outer_loss(const float *c, const float *w, uint32_t S_nerf, const float *cp, const float *wp, uint32_t S_prop, uint32_t N,
+                   float *loss_ray, float *dterm, ucn_stream_t stream);
 
 /* ------------------------------------------------- virtual-pose depth warping
  * ref: train_utils.py:19-55 img_warping / :58-98 img_warping_for_depth, called per training step on a full depth
@@ -697,6 +703,17 @@ int ucn_data_loss(const float *const *rgb_levels_host /*[L] device pointers, eac
                   const float *w_charb_host /*[L]*/, const float *target /*[N,3]*/, const float *lossmult /*[N]|NULL*/, uint32_t N,
                   float charb_padding, float *fwd_out /*[2 L + 2]*/, const float *g /*[1]|NULL*/, float *const *g_rgb_levels_host,
                   ucn_stream_t stream);
+/* ucn_data_loss_ex: ucn_data_loss with a third weight per level, w_raw (NULL = 0), for data_loss_type = 'rawnerf' (train_utils.py:195-202):
+ * rawnerf_l = sum(m (clip - target)^2 / (1e-3 + clip)^2) / sum(m), clip = min(rgb_l, 1), the 1 / (1e-3 + clip) factor detached; its backward
+ * is 2 (clip - target) / (1e-3 + clip)^2 where rgb_l <= 1 and 0 above (clamp_max).  fwd_out keeps ucn_data_loss's layout: the mse statistic is the
+ * unclipped residual, the loss at [2 L + 1] gains sum_l w_raw[l] rawnerf_l. */
+int ucn_data_loss_ex(const float *const *rgb_levels_host, uint32_t L, const float *w_mse_host, const float *w_charb_host,
+                     const float *w_raw_host /*[L]|NULL*/, const float *target, const float *lossmult, uint32_t N, float charb_padding,
+                     float *fwd_out /*[2 L + 2]*/, const float *g /*[1]|NULL*/, float *const *g_rgb_levels_host, ucn_stream_t stream);
+/* ucn_opacity_loss (train_utils.py:308-313): sum_l mult * mean(-acc_l log(acc_l + 1e-5)); backward d / d acc_l = -g mult (log(o + 1e-5) +
+ * o / (o + 1e-5)) / N.  L <= 4; one launch each way, terms formed and added in double. */
+int ucn_opacity_loss(const float *const *acc_levels_host /*[L] device pointers, each [N]*/, uint32_t L, uint32_t N, float mult,
+                     float *loss_out /*[1]*/, const float *g /*[1]|NULL*/, float *const *g_acc_levels_host, ucn_stream_t stream);
 /* ucn_sky_loss (train_utils.py:149-157): sum_l mean BCE(clip(acc_l, 1e-3, 0.999), 1 - sky_segs) */
 int ucn_sky_loss(const float *const *acc_levels_host /*[L] device pointers, each [N]*/, uint32_t L, const float *sky_segs /*[N]*/, uint32_t N,
                  float *loss_out /*[1]*/, const float *g /*[1]|NULL*/, float *const *g_acc_levels_host, ucn_stream_t stream);

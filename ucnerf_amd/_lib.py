@@ -11,7 +11,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # UCN_LIB_PATH: another build of the same ABI for A/B measurements; default = the in-tree product
 LIB_PATH = os.environ.get("UCN_LIB_PATH") or os.path.join(_HERE, "csrc", "libucnerf_march.so")
-ABI_VERSION = 29
+ABI_VERSION = 30
 LAUNCH_CORESIDENT = 0x100  # include/ucnerf_march.h UCN_LAUNCH_CORESIDENT
 TABLE_F16 = 0x200
 RAYS_INCOHERENT = 0x1000   # ucn_march_features layout flag: random (training) rays -> lane-paired fetch on every hashed level
@@ -117,6 +117,7 @@ SIGNATURES = {
     "ucn_img_warping": [c_vp, c_vp, c_vp, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp],
     "ucn_warp_scatter_depth": [c_vp, c_vp, c_vp, c_u32, c_u32, c_vp, c_vp, c_vp],
     "ucn_interlevel_loss": [c_vp, c_vp, c_u32, c_vp, c_vp, c_u32, c_f32, c_u32, c_vp, c_vp, c_vp],
+    "ucn_outer_loss": [c_vp, c_vp, c_u32, c_vp, c_vp, c_u32, c_u32, c_vp, c_vp, c_vp],
     "ucn_bias_relu": [c_vp, c_vp, c_u32, c_u32, c_u32, c_i32, c_vp],
     "ucn_relu_backward_reduce": [c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_u32, c_i32, c_vp],
     "ucn_ray_film": [c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_u32, c_i32, c_vp],
@@ -167,6 +168,8 @@ SIGNATURES = {
     "ucn_apply_affine": [c_vp, c_vp, c_vp, c_vp, c_u32, c_vp, c_vp, c_u32, c_vp, c_vp],
     "ucn_affine_blend": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "ucn_data_loss": [c_vp, c_u32, c_vp, c_vp, c_vp, c_vp, c_u32, ctypes.c_float, c_vp, c_vp, c_vp, c_vp],
+    "ucn_data_loss_ex": [c_vp, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, ctypes.c_float, c_vp, c_vp, c_vp, c_vp],
+    "ucn_opacity_loss": [c_vp, c_u32, c_u32, ctypes.c_float, c_vp, c_vp, c_vp, c_vp],
     "ucn_sky_loss": [c_vp, c_u32, c_vp, c_u32, c_vp, c_vp, c_vp, c_vp],
     "ucn_identity_loss": [c_vp, c_vp, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp],
 }

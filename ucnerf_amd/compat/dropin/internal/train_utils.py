@@ -3,8 +3,10 @@ every helper train.py / datasets.py / eval.py use -- tree_len, GradientScaler, i
 orientation / normal losses ... -- is there unchanged) with the functions on the training step's hot path replaced by
 this repo's device implementations of the same name and signature (train.py:102, 173-216, 221):
 
-    compute_data_loss       one set of launches for all levels, stats fetched lazily (no host sync inside the step)
+    compute_data_loss       one set of launches for all levels ('mse', 'charb', 'rawnerf'), stats fetched lazily (no host sync inside the step)
     anti_interlevel_loss    ucn_interlevel_loss
+    interlevel_loss         ucn_outer_loss (mip-NeRF 360), one launch per proposal level
+    opacity_loss            ucn_opacity_loss, one launch for all levels
     distortion_loss         ucn_distortion_loss, O(S) per ray
     hash_decay_loss         reads ray_history[...]['loss_hash_decay'] (ucn_hash_decay inside the model)
     sky_loss, transformIdentityLoss
@@ -26,4 +28,4 @@ upstream = _up
 
 from ucnerf_amd.internal.train_utils import (FusedAdam, LazyStats, anti_interlevel_loss, clip_gradients,  # noqa: E402,F401
                                              compute_data_loss, create_optimizer, distortion_loss, hash_decay_loss,
-                                             sky_loss, transformIdentityLoss)
+                                             interlevel_loss, opacity_loss, sky_loss, transformIdentityLoss)

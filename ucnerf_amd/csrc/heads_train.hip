@@ -96,13 +96,16 @@ struct LevelPtrs {
 struct LevelOut {
     float *p[kMaxLossLevels];
 };
-struct LevelWeights {                                   // loss = sum_l  w_mse[l] mse_l + w_charb[l] charb_l
-    float w_mse[kMaxLossLevels], w_charb[kMaxLossLevels];
+struct LevelWeights {                                   // loss = sum_l  w_mse[l] mse_l + w_charb[l] charb_l + w_raw[l] rawnerf_l
+    float w_mse[kMaxLossLevels], w_charb[kMaxLossLevels], w_raw[kMaxLossLevels];
 };
 
 // train_utils.py:171-230: per level l  mse_l = sum(m r^2) / sum(m),  charb_l = sum(m sqrt(r^2 + pad^2)) / sum(m),  r = rgb_l - target,
 // m = lossmult (per ray, broadcast over the channels; NULL = 1).  ONE workgroup (the batch is 8192 rays): fixed-order sums.
 // out: [L][2] = {mse, charb}, the denominator at [2 L], the weighted loss at [2 L + 1].
+// rawnerf_l (train_utils.py:195-202) = sum(m (clip - target)^2 / (1e-3 + clip)^2) / sum(m), clip = min(rgb_l, 1); the mse statistic
+// stays the unclipped residual.  Its terms span 1e6 (the 1e-3 in the denominator): a call with any w_raw != 0 takes k_data_loss_fwd_raw,
+// which forms and adds every sum (the denominator and the statistics too) in double; the float kernel and its bits are untouched.
 __global__ __launch_bounds__(1024) void k_data_loss_fwd(LevelPtrs rgb, uint32_t L, LevelWeights w, const float *__restrict__ target,
                                                         const float *__restrict__ mult, uint32_t N, float pad2, float *__restrict__ out) {
     __shared__ float scratch[1024];
@@ -123,6 +126,33 @@ __global__ __launch_bounds__(1024) void k_data_loss_fwd(LevelPtrs rgb, uint32_t 
     }
     if (threadIdx.x == 0) { out[2 * L] = den; out[2 * L + 1] = loss; }
 }
+// The same outputs with the rawnerf term, every sum in double (8 KB of LDS, one pass per level; the Charbonnier sum only where its
+// weight is not 0).  The backward divides by the float out[2 L] this kernel stores, the forward by the double it was rounded from: the
+// stored gradient is the derivative of the returned value up to that one rounding (2^-24 relative).
+__global__ __launch_bounds__(1024) void k_data_loss_fwd_raw(LevelPtrs rgb, uint32_t L, LevelWeights w, const float *__restrict__ target,
+                                                            const float *__restrict__ mult, uint32_t N, float pad2, float *__restrict__ out) {
+    __shared__ double scratch[1024];
+    double den = 0.0, loss = 0.0;
+    for (uint32_t i = threadIdx.x; i < N * 3u; i += 1024u) den += (double)(mult ? mult[i / 3u] : 1.0f);
+    den = wg_sum_1024(den, scratch);
+    for (uint32_t l = 0; l < L; l++) {
+        const bool charb = w.w_charb[l] != 0.0f;
+        double a = 0.0, c = 0.0, rw = 0.0;
+        for (uint32_t i = threadIdx.x; i < N * 3u; i += 1024u) {
+            const double m = (double)(mult ? mult[i / 3u] : 1.0f), x = (double)rgb.p[l][i], t = (double)target[i];
+            const double r = x - t, clip = x < 1.0 ? x : 1.0, rc = clip - t, s = 1e-3 + clip;
+            a += m * (r * r);
+            if (charb) c += m * sqrt(r * r + (double)pad2);
+            rw += m * (rc * rc) / (s * s);
+        }
+        a = wg_sum_1024(a, scratch);
+        if (charb) c = wg_sum_1024(c, scratch);
+        rw = wg_sum_1024(rw, scratch);
+        if (threadIdx.x == 0) { out[2 * l] = (float)(a / den); out[2 * l + 1] = (float)(c / den); }
+        loss += (double)w.w_mse[l] * (a / den) + (double)w.w_charb[l] * (c / den) + (double)w.w_raw[l] * (rw / den);
+    }
+    if (threadIdx.x == 0) { out[2 * L] = (float)den; out[2 * L + 1] = (float)loss; }
+}
 // g: [1] = d / d loss
 __global__ __launch_bounds__(256) void k_data_loss_bwd(LevelPtrs rgb, LevelOut g_rgb, uint32_t L, LevelWeights w, const float *__restrict__ target,
                                                        const float *__restrict__ mult, uint32_t N, float pad2,
@@ -132,7 +162,14 @@ __global__ __launch_bounds__(256) void k_data_loss_bwd(LevelPtrs rgb, LevelOut g
     const float m = (mult ? mult[i / 3u] : 1.0f) / fwd_out[2 * L];
     for (uint32_t l = 0; l < L; l++) {
         const float r = rgb.p[l][i] - target[i], r2 = r * r;
-        g_rgb.p[l][i] = g[0] * m * (w.w_mse[l] * 2.0f * r + w.w_charb[l] * r / sqrtf(r2 + pad2));
+        float gl = g[0] * m * (w.w_mse[l] * 2.0f * r + w.w_charb[l] * r / sqrtf(r2 + pad2));
+        if (w.w_raw[l] != 0.0f) {
+            // clamp_max's backward: 1 where rgb <= 1 (the bound included, like torch), 0 above; the 1 / (1e-3 + clip) factor is detached
+            const float x = rgb.p[l][i];
+            const double s = 1e-3 + (double)x;
+            if (x <= 1.0f) gl += (float)((double)g[0] * (double)m * (double)w.w_raw[l] * 2.0 * ((double)x - (double)target[i]) / (s * s));
+        }
+        g_rgb.p[l][i] = gl;
     }
 }
 
@@ -162,6 +199,33 @@ __global__ __launch_bounds__(256) void k_sky_loss_bwd(LevelPtrs acc, LevelOut g_
         const bool inside = raw >= 1e-3f && raw <= 0.999f;              // clip's gradient: 1 inside (torch: bounds included), 0 outside
         const float a = fminf(fmaxf(raw, 1e-3f), 0.999f);
         g_acc.p[l][i] = inside ? go * (a - t) / (a * (1.0f - a)) : 0.0f;
+    }
+}
+
+// train_utils.py:308-313: sum over the levels of mult * mean(-o log(o + 1e-5)), o = acc.  The terms are formed and added in double
+// (log is the only transcendental of the step's loss tail that is differenced against 0 at o -> 1).
+__global__ __launch_bounds__(1024) void k_opacity_loss_fwd(LevelPtrs acc, uint32_t L, uint32_t N, float mult, float *__restrict__ out) {
+    __shared__ double scratch[1024];
+    double tot = 0.0;
+    for (uint32_t l = 0; l < L; l++) {
+        double s = 0.0;
+        for (uint32_t i = threadIdx.x; i < N; i += 1024u) {
+            const double o = (double)acc.p[l][i];
+            s -= o * log(o + 1e-5);
+        }
+        s = wg_sum_1024(s, scratch);
+        tot += (double)mult * (s / (double)N);
+    }
+    if (threadIdx.x == 0) out[0] = (float)tot;
+}
+__global__ __launch_bounds__(256) void k_opacity_loss_bwd(LevelPtrs acc, LevelOut g_acc, uint32_t L, uint32_t N, float mult,
+                                                          const float *__restrict__ g) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= N) return;
+    const double go = (double)g[0] * (double)mult / (double)N;
+    for (uint32_t l = 0; l < L; l++) {
+        const double o = (double)acc.p[l][i];
+        g_acc.p[l][i] = (float)(-go * (log(o + 1e-5) + o / (o + 1e-5)));
     }
 }
 
@@ -211,9 +275,10 @@ extern "C" int ucn_affine_blend(const float *g_out, const float *rgb, const floa
     return 0;
 }
 
-extern "C" int ucn_data_loss(const float *const *rgb_levels_host, uint32_t L, const float *w_mse_host, const float *w_charb_host,
-                             const float *target, const float *lossmult, uint32_t N, float charb_padding, float *fwd_out /*[2 L + 2]*/,
-                             const float *g /*[1] or NULL*/, float *const *g_rgb_levels_host, ucn_stream_t stream) {
+extern "C" int ucn_data_loss_ex(const float *const *rgb_levels_host, uint32_t L, const float *w_mse_host, const float *w_charb_host,
+                                const float *w_raw_host /*[L] or NULL = 0*/, const float *target, const float *lossmult, uint32_t N,
+                                float charb_padding, float *fwd_out /*[2 L + 2]*/, const float *g /*[1] or NULL*/,
+                                float *const *g_rgb_levels_host, ucn_stream_t stream) {
     UCN_REQUIRE(L >= 1 && L <= kMaxLossLevels, "data_loss: 1 to %u levels", kMaxLossLevels);
     UCN_REQUIRE(rgb_levels_host && w_mse_host && w_charb_host && target && fwd_out && ((g == nullptr) == (g_rgb_levels_host == nullptr)),
                 "data_loss: null pointer argument");
@@ -226,12 +291,40 @@ extern "C" int ucn_data_loss(const float *const *rgb_levels_host, uint32_t L, co
         go.p[l] = (g && l < L) ? g_rgb_levels_host[l] : nullptr;
         w.w_mse[l] = l < L ? w_mse_host[l] : 0.0f;
         w.w_charb[l] = l < L ? w_charb_host[l] : 0.0f;
+        w.w_raw[l] = (w_raw_host && l < L) ? w_raw_host[l] : 0.0f;
     }
     const float pad2 = charb_padding * charb_padding;
-    if (!g) hipLaunchKernelGGL(k_data_loss_fwd, dim3(1), dim3(1024), 0, (hipStream_t)stream, in, L, w, target, lossmult, N, pad2, fwd_out);
+    bool any_raw = false;
+    for (uint32_t l = 0; l < L; l++) any_raw = any_raw || w.w_raw[l] != 0.0f;
+    if (!g && any_raw) hipLaunchKernelGGL(k_data_loss_fwd_raw, dim3(1), dim3(1024), 0, (hipStream_t)stream, in, L, w, target, lossmult, N, pad2, fwd_out);
+    else if (!g) hipLaunchKernelGGL(k_data_loss_fwd, dim3(1), dim3(1024), 0, (hipStream_t)stream, in, L, w, target, lossmult, N, pad2, fwd_out);
     else hipLaunchKernelGGL(k_data_loss_bwd, dim3(ucn_div_up((uint64_t)N * 3u, 256)), dim3(256), 0, (hipStream_t)stream, in, go, L, w, target,
                             lossmult, N, pad2, fwd_out, g);
     UCN_LAUNCH_CHECK("data_loss");
+    return 0;
+}
+
+extern "C" int ucn_data_loss(const float *const *rgb_levels_host, uint32_t L, const float *w_mse_host, const float *w_charb_host,
+                             const float *target, const float *lossmult, uint32_t N, float charb_padding, float *fwd_out /*[2 L + 2]*/,
+                             const float *g /*[1] or NULL*/, float *const *g_rgb_levels_host, ucn_stream_t stream) {
+    return ucn_data_loss_ex(rgb_levels_host, L, w_mse_host, w_charb_host, nullptr, target, lossmult, N, charb_padding, fwd_out, g,
+                            g_rgb_levels_host, stream);
+}
+
+extern "C" int ucn_opacity_loss(const float *const *acc_levels_host, uint32_t L, uint32_t N, float mult, float *loss_out,
+                                const float *g /*[1] or NULL*/, float *const *g_acc_levels_host, ucn_stream_t stream) {
+    UCN_REQUIRE(L >= 1 && L <= kMaxLossLevels, "opacity_loss: 1 to %u levels", kMaxLossLevels);
+    UCN_REQUIRE(acc_levels_host && ((g == nullptr) == (g_acc_levels_host == nullptr)) && (g || loss_out), "opacity_loss: null pointer argument");
+    if (N == 0) return 0;
+    LevelPtrs in;
+    LevelOut go;
+    for (uint32_t l = 0; l < kMaxLossLevels; l++) {
+        in.p[l] = l < L ? acc_levels_host[l] : nullptr;
+        go.p[l] = (g && l < L) ? g_acc_levels_host[l] : nullptr;
+    }
+    if (!g) hipLaunchKernelGGL(k_opacity_loss_fwd, dim3(1), dim3(1024), 0, (hipStream_t)stream, in, L, N, mult, loss_out);
+    else hipLaunchKernelGGL(k_opacity_loss_bwd, dim3(ucn_div_up(N, 256)), dim3(256), 0, (hipStream_t)stream, in, go, L, N, mult, g);
+    UCN_LAUNCH_CHECK("opacity_loss");
     return 0;
 }
 

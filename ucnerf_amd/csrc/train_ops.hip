@@ -223,6 +223,111 @@ __global__ __launch_bounds__(256) void k_interlevel(const float *__restrict__ c_
     if (lane == 0 && live) loss_ray[ray] = acc;
 }
 
+// mip-NeRF 360 interlevel loss for one proposal level (train_utils.py:233-244, stepfun.py:6-61 lossfun_outer / inner_outer):
+// the proposal histogram (cp, wp) has to be an upper envelope of the NeRF histogram (c, w).  With cy = [0, cumsum(wp)],
+//   lo(v) = largest k with cp[k] <= v (0 if none),  hi(v) = smallest k with cp[k] > v (Sp if none)      (stepfun.py:21-25)
+//   w_outer[i] = cy[hi(c[i+1])] - cy[lo(c[i])],  loss[i] = max(w[i] - w_outer[i], 0)^2 / (w[i] + FLT_EPSILON).
+// Only wp carries a gradient: d loss / d wp[k] = sum of g[i] = -2 max(w[i] - w_outer[i], 0) / (w[i] + eps) over the NeRF
+// intervals with lo(c[i]) <= k < hi(c[i+1]).  c and cp are sorted, so lo and hi are monotone in i and those intervals are
+// the contiguous range [a_k, b_k): a_k = #{i : c[i+1] < cp[k]} (hi(c[i+1]) <= k  <=>  cp[k] > c[i+1]) and
+// b_k = #{i : c[i] < cp[k+1]} (lo(c[i]) <= k  <=>  cp[k+1] > c[i]).  The gradient is P[b_k] - P[a_k] with P the exclusive
+// prefix sum of g: a lookup, no scatter and no atomics, the same bits on every call.  One wave per ray; the reference's
+// [S_prop+1, S_nerf+1] comparison masks are binary searches in LDS; both prefix sums accumulate in double (torch-CPU's
+// cumsum does) and cy is rounded to float like the reference's tensor, so w_outer sees the reference's own operands.
+__global__ __launch_bounds__(256) void k_outer_loss(const float *__restrict__ c_, const float *__restrict__ w_, uint32_t S1,
+                                                    const float *__restrict__ cp_, const float *__restrict__ wp_, uint32_t Sp, uint32_t N,
+                                                    float *__restrict__ loss_ray, float *__restrict__ dterm) {
+    extern __shared__ double s_ol[];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const uint32_t ray_raw = blockIdx.x * 4u + wv;
+    const bool live = ray_raw < N;
+    const uint32_t ray = live ? ray_raw : N - 1;
+    const uint32_t n1 = S1 + 1, np = Sp + 1;
+    const uint32_t region = n1 + ((n1 + 2 * np + 1) >> 1);            // doubles per wave: P[n1], then c[n1], cp[np], cy[np] as floats
+    double *P = s_ol + (size_t)wv * region;
+    float *c = reinterpret_cast<float *>(P + n1), *cp = c + n1, *cy = cp + np;
+    for (uint32_t i = lane; i < n1; i += 64) c[i] = c_[(size_t)ray * n1 + i];
+    for (uint32_t j = lane; j < np; j += 64) cp[j] = cp_[(size_t)ray * np + j];
+    // cy = [0, cumsum(wp)]: lane owns CHP consecutive proposal intervals
+    const uint32_t CHP = (Sp + 63) / 64;
+    double part = 0.0;
+    for (uint32_t q = 0; q < CHP; q++) {
+        const uint32_t k = lane * CHP + q;
+        if (k < Sp) part += (double)wp_[(size_t)ray * Sp + k];
+    }
+    double run = wscan_d(part, lane) - part;
+    for (uint32_t q = 0; q < CHP; q++) {
+        const uint32_t k = lane * CHP + q;
+        if (k < Sp) {
+            run += (double)wp_[(size_t)ray * Sp + k];
+            cy[k + 1] = (float)run;
+        }
+    }
+    if (lane == 0) cy[0] = 0.0f;
+    __syncthreads();
+    // per NeRF interval: the envelope weight, the loss term and g; lane owns CH1 (<= 8) consecutive intervals
+    const uint32_t CH1 = (S1 + 63) / 64;
+    float g[8];
+    double lsum = 0.0, gsum = 0.0;
+#pragma unroll
+    for (uint32_t q = 0; q < 8; q++) {
+        const uint32_t i = lane * CH1 + q;
+        g[q] = 0.0f;
+        if (q < CH1 && i < S1) {
+            const float v0 = c[i], v1 = c[i + 1];
+            uint32_t lo = 0, hi = np;                        // #(cp <= v0)
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (cp[mid] <= v0) lo = mid + 1;
+                else hi = mid;
+            }
+            const uint32_t k_lo = lo > 0 ? lo - 1 : 0;
+            lo = 0, hi = np;                                 // #(cp <= v1) = the first fencepost above v1
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (cp[mid] <= v1) lo = mid + 1;
+                else hi = mid;
+            }
+            const uint32_t k_hi = lo < Sp ? lo : Sp;
+            const float wi = w_[(size_t)ray * S1 + i], w_outer = cy[k_hi] - cy[k_lo];
+            const float ex = fmaxf(wi - w_outer, 0.0f), den = wi + 1.1920928955078125e-07f;
+            lsum += (double)(ex * ex / den);
+            g[q] = -2.0f * ex / den;
+            gsum += (double)g[q];
+        }
+    }
+    double prun = wscan_d(gsum, lane) - gsum;
+#pragma unroll
+    for (uint32_t q = 0; q < 8; q++) {
+        const uint32_t i = lane * CH1 + q;
+        if (q < CH1 && i < S1) {
+            P[i] = prun;
+            prun += (double)g[q];
+            if (i == S1 - 1) P[S1] = prun;
+        }
+    }
+    lsum = wave_sum_dpp<double>(lsum);
+    if (lane == 0 && live) loss_ray[ray] = (float)lsum;
+    __syncthreads();
+    for (uint32_t k = lane; k < Sp; k += 64) {
+        const float x0 = cp[k], x1 = cp[k + 1];
+        uint32_t lo = 0, hi = S1;                            // a = #{i < S1 : c[i+1] < x0}
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (c[mid + 1] < x0) lo = mid + 1;
+            else hi = mid;
+        }
+        const uint32_t a = lo;
+        lo = 0, hi = S1;                                     // b = #{i < S1 : c[i] < x1}
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (c[mid] < x1) lo = mid + 1;
+            else hi = mid;
+        }
+        if (live) dterm[(size_t)ray * Sp + k] = (float)(P[lo] - P[a]);
+    }
+}
+
 // ---- elementwise halves of the colour MLP's hidden layers in training (models.py:615-640 under autograd).
 // The reference concatenates the per-ray direction encoding to every sample; here it enters as a per-RAY row
 // (direction block of the weight times the encoding, plus the bias) that is broadcast over the ray's S samples:
@@ -608,6 +713,20 @@ extern "C" int ucn_interlevel_loss(const float *c, const float *w, uint32_t S_ne
     hipLaunchKernelGGL(k_interlevel, dim3(ucn_div_up(N, 4)), dim3(256), lds, (hipStream_t)stream, c, w, S_nerf, cp, wp, S_prop, pulse_width,
                        N, loss_ray, dterm);
     UCN_LAUNCH_CHECK("interlevel_loss");
+    return 0;
+}
+
+extern "C" int ucn_outer_loss(const float *c, const float *w, uint32_t S_nerf, const float *cp, const float *wp, uint32_t S_prop, uint32_t N,
+                              float *loss_ray, float *dterm, ucn_stream_t stream) {
+    if (N == 0) return 0;
+    UCN_REQUIRE(c && w && cp && wp && loss_ray && dterm, "outer_loss: null pointer argument");
+    UCN_REQUIRE(S_nerf >= 1 && S_nerf <= 512 && S_prop >= 1 && S_prop <= 1024, "outer_loss: unsupported sample counts %u / %u", S_nerf,
+                S_prop);
+    const uint32_t n1 = S_nerf + 1, np = S_prop + 1;
+    const size_t lds = 4 * sizeof(double) * ((size_t)n1 + ((n1 + 2 * np + 1) >> 1));      // <= 57 440 bytes at 512 / 1024
+    hipLaunchKernelGGL(k_outer_loss, dim3(ucn_div_up(N, 4)), dim3(256), lds, (hipStream_t)stream, c, w, S_nerf, cp, wp, S_prop, N, loss_ray,
+                       dterm);
+    UCN_LAUNCH_CHECK("outer_loss");
     return 0;
 }
 

@@ -96,22 +96,63 @@ class _InterLevel(torch.autograd.Function):
     def forward(ctx, c, w, cp, wp, r):
         lib = _lib.load()
         S1, Sp = w.shape[-1], wp.shape[-1]
-        c2, w2 = c.reshape(-1, S1 + 1).contiguous(), w.reshape(-1, S1).contiguous()
-        cp2, wp2 = cp.reshape(-1, Sp + 1).contiguous(), wp.reshape(-1, Sp).contiguous()
+        c2, w2 = c.reshape(-1, S1 + 1).float().contiguous(), w.reshape(-1, S1).float().contiguous()    # (half inputs outside autocast)
+        cp2, wp2 = cp.reshape(-1, Sp + 1).float().contiguous(), wp.reshape(-1, Sp).float().contiguous()
         N = w2.shape[0]
         loss_ray = torch.empty(N, device=w.device)
         dterm = torch.empty(N, Sp, device=w.device)
         _lib.check(lib.ucn_interlevel_loss(c2.data_ptr(), w2.data_ptr(), S1, cp2.data_ptr(), wp2.data_ptr(), Sp, float(r), N,
                                            loss_ray.data_ptr(), dterm.data_ptr(), _lib.stream()))
         ctx.save_for_backward(dterm)
-        ctx.shape = wp.shape
+        ctx.shape, ctx.dtype = wp.shape, wp.dtype
         return loss_ray.sum() / (N * Sp)
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, g):
         (dterm,) = ctx.saved_tensors
-        return None, None, None, (dterm * (g / dterm.numel())).reshape(ctx.shape), None
+        return None, None, None, (dterm * (g / dterm.numel())).reshape(ctx.shape).to(ctx.dtype), None
+
+
+class _OuterLevel(torch.autograd.Function):
+    """One proposal level of interlevel_loss (mip-NeRF 360) as the HIP kernel `ucn_outer_loss`: mean over rays and NeRF
+    intervals of max(w - w_outer, 0)^2 / (w + eps); the NeRF level (c, w) and the fenceposts cp are constants.  The kernel
+    leaves d loss_ray / d wp, the backward is a scale of it."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, c, w, cp, wp):
+        lib = _lib.load()
+        S1, Sp = w.shape[-1], wp.shape[-1]
+        c2, w2 = c.reshape(-1, S1 + 1).float().contiguous(), w.reshape(-1, S1).float().contiguous()    # (half inputs outside autocast)
+        cp2, wp2 = cp.reshape(-1, Sp + 1).float().contiguous(), wp.reshape(-1, Sp).float().contiguous()
+        N = w2.shape[0]
+        assert c2.shape[0] == N and cp2.shape[0] == N and wp2.shape[0] == N, (c.shape, w.shape, cp.shape, wp.shape)
+        loss_ray = torch.empty(N, device=w.device)
+        dterm = torch.empty(N, Sp, device=w.device)
+        _lib.check(lib.ucn_outer_loss(c2.data_ptr(), w2.data_ptr(), S1, cp2.data_ptr(), wp2.data_ptr(), Sp, N, loss_ray.data_ptr(),
+                                      dterm.data_ptr(), _lib.stream()))
+        ctx.save_for_backward(dterm)
+        ctx.shape, ctx.count, ctx.dtype = wp.shape, N * S1, wp.dtype
+        return (loss_ray.sum(dtype=torch.float64) / (N * S1)).float()
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, g):
+        (dterm,) = ctx.saved_tensors
+        return None, None, None, (dterm * (g / ctx.count)).reshape(ctx.shape).to(ctx.dtype)
+
+
+def _outer_level_torch(c, w, cp, wp):
+    """stepfun.py:52-61 lossfun_outer(c, w, cp, wp).mean() with the [S_prop+1, S_nerf+1] masks of stepfun.py:21-25 as two
+    binary searches: idx_lo = (#cp <= v) - 1 clamped at 0, idx_hi = #cp <= v clamped at S_prop.  Any device, any gradient."""
+    Sp = wp.shape[-1]
+    cp_, c_ = cp.detach().contiguous(), c.detach().contiguous()
+    lo = (torch.searchsorted(cp_, c_[..., :-1].contiguous(), right=True) - 1).clamp_min(0)
+    hi = torch.searchsorted(cp_, c_[..., 1:].contiguous(), right=True).clamp_max(Sp)
+    cy = torch.cat([torch.zeros_like(wp[..., :1]), torch.cumsum(wp, dim=-1)], dim=-1)
+    w_outer = cy.gather(-1, hi) - cy.gather(-1, lo)
+    return ((w - w_outer).clamp_min(0) ** 2 / (w + torch.finfo(c.dtype).eps)).mean()
 
 
 # ------------------------------------------------------------------ losses (train.py:173-216)
@@ -153,21 +194,22 @@ class LazyStats(collections.abc.MutableMapping):
 
 
 class _DataLoss(torch.autograd.Function):
-    """train_utils.py:171-230 for all levels in ONE launch forward + one backward (`ucn_data_loss`): the weighted loss and the
-    per-level mse statistics; ~10 + ~15 eager launches otherwise."""
+    """train_utils.py:171-230 for all levels in ONE launch forward + one backward (`ucn_data_loss_ex`): the weighted loss
+    ('mse', 'charb' or 'rawnerf' weights per level) and the per-level mse statistics; ~10 + ~15 eager launches otherwise."""
 
     @staticmethod
-    def forward(ctx, target, mult, pad, w_mse, w_charb, *levels):
+    def forward(ctx, target, mult, pad, w_mse, w_charb, w_raw, *levels):
         lib = _lib.load()
         N = target.shape[0]
         L = len(levels)
         levels = [l.contiguous() for l in levels]
         out = torch.empty(2 * L + 2, device=target.device)
-        wm, wc = (ctypes.c_float * L)(*w_mse), (ctypes.c_float * L)(*w_charb)
+        wm, wc, wr = (ctypes.c_float * L)(*w_mse), (ctypes.c_float * L)(*w_charb), (ctypes.c_float * L)(*w_raw)
         ptrs = (ctypes.c_void_p * L)(*[l.data_ptr() for l in levels])
-        _lib.check(lib.ucn_data_loss(ptrs, L, wm, wc, target.data_ptr(), _lib.ptr(mult), N, float(pad), out.data_ptr(), None, None, _lib.stream()))
+        _lib.check(lib.ucn_data_loss_ex(ptrs, L, wm, wc, wr, target.data_ptr(), _lib.ptr(mult), N, float(pad), out.data_ptr(), None, None,
+                                        _lib.stream()))
         ctx.save_for_backward(target, out, *levels)
-        ctx.mult, ctx.pad, ctx.w = mult, float(pad), (list(w_mse), list(w_charb))
+        ctx.mult, ctx.pad, ctx.w = mult, float(pad), (list(w_mse), list(w_charb), list(w_raw))
         ctx.mark_non_differentiable(out)
         return out[2 * L + 1], out
 
@@ -178,12 +220,12 @@ class _DataLoss(torch.autograd.Function):
         N, L = target.shape[0], len(levels)
         g = g_loss.reshape(1).float().contiguous()
         grads = [torch.empty_like(l) for l in levels]
-        wm, wc = (ctypes.c_float * L)(*ctx.w[0]), (ctypes.c_float * L)(*ctx.w[1])
+        wm, wc, wr = (ctypes.c_float * L)(*ctx.w[0]), (ctypes.c_float * L)(*ctx.w[1]), (ctypes.c_float * L)(*ctx.w[2])
         ptrs = (ctypes.c_void_p * L)(*[l.data_ptr() for l in levels])
         gptrs = (ctypes.c_void_p * L)(*[x.data_ptr() for x in grads])
-        _lib.check(lib.ucn_data_loss(ptrs, L, wm, wc, target.data_ptr(), _lib.ptr(ctx.mult), N, ctx.pad, out.data_ptr(), g.data_ptr(), gptrs,
-                                     _lib.stream()))
-        return (None, None, None, None, None, *grads)
+        _lib.check(lib.ucn_data_loss_ex(ptrs, L, wm, wc, wr, target.data_ptr(), _lib.ptr(ctx.mult), N, ctx.pad, out.data_ptr(), g.data_ptr(),
+                                        gptrs, _lib.stream()))
+        return (None, None, None, None, None, None, *grads)
 
 
 class _SkyLoss(torch.autograd.Function):
@@ -210,6 +252,34 @@ class _SkyLoss(torch.autograd.Function):
         ptrs = (ctypes.c_void_p * L)(*[a.data_ptr() for a in accs])
         gptrs = (ctypes.c_void_p * L)(*[x.data_ptr() for x in grads])
         _lib.check(lib.ucn_sky_loss(ptrs, L, sky_segs.data_ptr(), N, None, g.data_ptr(), gptrs, _lib.stream()))
+        return (None, *grads)
+
+
+class _OpacityLoss(torch.autograd.Function):
+    """train_utils.py:308-313 over all levels: one launch forward, one backward (`ucn_opacity_loss`)."""
+
+    @staticmethod
+    def forward(ctx, mult, *accs):
+        lib = _lib.load()
+        accs = [a.contiguous() for a in accs]
+        N, L = accs[0].shape[0], len(accs)
+        out = torch.empty(1, device=accs[0].device)
+        ptrs = (ctypes.c_void_p * L)(*[a.data_ptr() for a in accs])
+        _lib.check(lib.ucn_opacity_loss(ptrs, L, N, float(mult), out.data_ptr(), None, None, _lib.stream()))
+        ctx.save_for_backward(*accs)
+        ctx.mult = float(mult)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        accs = ctx.saved_tensors
+        N, L = accs[0].shape[0], len(accs)
+        g = g.reshape(1).float().contiguous()
+        grads = [torch.empty_like(a) for a in accs]
+        ptrs = (ctypes.c_void_p * L)(*[a.data_ptr() for a in accs])
+        gptrs = (ctypes.c_void_p * L)(*[x.data_ptr() for x in grads])
+        _lib.check(lib.ucn_opacity_loss(ptrs, L, N, ctx.mult, None, g.data_ptr(), gptrs, _lib.stream()))
         return (None, *grads)
 
 
@@ -245,12 +315,20 @@ def _f32_cuda(*tensors, half_ok=False):
     return all(t.is_cuda and t.dtype in ok for t in tensors)
 
 
+def _level_pair_on_device(c, w, cp, wp):
+    """the two step functions a per-ray loss kernel can be handed as raw pointers: float (or half, upcast by the node) device tensors,
+    fenceposts one longer than weights, the same rays on both sides, no gradient into the proposal fenceposts"""
+    S1, Sp = w.shape[-1], wp.shape[-1]
+    return (_f32_cuda(c, w, cp, wp, half_ok=True) and not cp.requires_grad and S1 >= 1 and Sp >= 1 and c.shape[-1] == S1 + 1
+            and cp.shape[-1] == Sp + 1 and c.numel() // (S1 + 1) == w.numel() // S1 == cp.numel() // (Sp + 1) == wp.numel() // Sp)
+
+
 def compute_data_loss(batch, renderings, config):
-    """ref train_utils.py:171-230 ('mse' and 'charb').  All levels in one set of elementwise / reduce launches (the
+    """ref train_utils.py:171-230 ('mse', 'charb' and 'rawnerf').  All levels in one set of elementwise / reduce launches (the
     levels' rgb stacked), the per-level mse statistics handed back as LazyStats."""
     target = batch['rgb'][..., :3]
     kind = getattr(config, 'data_loss_type', 'charb')
-    if kind not in ('mse', 'charb'):
+    if kind not in ('mse', 'charb', 'rawnerf'):
         raise NotImplementedError(f"data_loss_type={kind!r}")
     n_lvl = len(renderings)
     coarse = getattr(config, 'data_coarse_loss_mult', 0.)
@@ -261,26 +339,57 @@ def compute_data_loss(batch, renderings, config):
         N = target.numel() // 3
         mult = None if getattr(config, 'disable_multiscale_loss', False) else batch['lossmult'].reshape(N).float().contiguous()
         w_level = [coarse if (coarse != 0 and n_lvl > 1) else 0.0] * (n_lvl - 1) + [getattr(config, 'data_loss_mult', 1.0)]
-        w_mse = w_level if kind == 'mse' else [0.0] * n_lvl
-        w_charb = [0.0] * n_lvl if kind == 'mse' else w_level
+        w_mse, w_charb, w_raw = [w_level if kind == k else [0.0] * n_lvl for k in ('mse', 'charb', 'rawnerf')]
         loss, out = _DataLoss.apply(target.reshape(N, 3).contiguous(), mult, getattr(config, 'charb_padding', 0.001), w_mse, w_charb,
-                                    *[l.reshape(N, 3) for l in levels])
+                                    w_raw, *[l.reshape(N, 3) for l in levels])
         return loss, LazyStats(mses=out[0:2 * n_lvl:2])
     lossmult = torch.broadcast_to(batch['lossmult'], target.shape)
     if getattr(config, 'disable_multiscale_loss', False):
         lossmult = torch.ones_like(lossmult)
     denom = lossmult.sum()
     dims = tuple(range(1, target.dim() + 1))
-    resid_sq = (torch.stack([r['rgb'] for r in renderings]) - target) ** 2                # [levels, ...]
+    rgb = torch.stack([r['rgb'] for r in renderings])
+    resid_sq = (rgb - target) ** 2                                                         # [levels, ...]
     mses = (lossmult * resid_sq).sum(dim=dims) / denom
     if kind == 'mse':
         per_level = mses
+    elif kind == 'rawnerf':
+        clip = rgb.clamp_max(1)                                                            # sensor overexposure (train_utils.py:196-202)
+        per_level = (lossmult * ((clip - target) ** 2 * (1. / (1e-3 + clip.detach())) ** 2)).sum(dim=dims) / denom
     else:
         per_level = (lossmult * torch.sqrt(resid_sq + getattr(config, 'charb_padding', 0.001) ** 2)).sum(dim=dims) / denom
     loss = getattr(config, 'data_loss_mult', 1.0) * per_level[-1]
     if coarse != 0 and n_lvl > 1:
         loss = loss + coarse * per_level[:-1].sum()
     return loss, LazyStats(mses=mses.detach())
+
+
+def interlevel_loss(ray_history, config):
+    """ref train_utils.py:233-244 (mip-NeRF 360).  Device tensors whose proposal fenceposts carry no gradient take the HIP
+    kernel, one launch per proposal level; `_outer_level_torch` is the general form."""
+    c = ray_history[-1]['sdist'].detach()
+    w = ray_history[-1]['weights'].detach()
+    total = 0.
+    for level in ray_history[:-1]:
+        cp, wp = level['sdist'], level['weights']
+        if _level_pair_on_device(c, w, cp, wp) and w.shape[-1] <= 512 and wp.shape[-1] <= 1024:
+            total = total + _OuterLevel.apply(c, w, cp, wp)
+        else:
+            total = total + _outer_level_torch(c, w, cp, wp)
+    return getattr(config, 'interlevel_loss_mult', 0.) * total
+
+
+def opacity_loss(renderings, config):
+    """ref train_utils.py:308-313."""
+    mult = getattr(config, 'opacity_loss_mult', 0.)
+    accs = [r['acc'] for r in renderings]
+    if 1 <= len(accs) <= 4 and _f32_cuda(*accs) and all(a.numel() == accs[0].numel() for a in accs) and accs[0].numel() > 0:
+        N = accs[0].numel()
+        return _OpacityLoss.apply(mult, *[a.reshape(N) for a in accs])          # one HIP node for all levels (csrc/heads_train.hip)
+    total = 0.
+    for o in accs:
+        total = total + mult * (-o * torch.log(o + 1e-5)).mean()
+    return total
 
 
 def anti_interlevel_loss(ray_history, config):
@@ -292,7 +401,7 @@ def anti_interlevel_loss(ray_history, config):
     widths = getattr(config, 'pulse_width', [0.03, 0.003])
     for i, level in enumerate(ray_history[:-1]):
         cp, wp = level['sdist'], level['weights']
-        if wp.is_cuda and not cp.requires_grad and w.shape[-1] <= 512:
+        if _level_pair_on_device(c, w, cp, wp) and w.shape[-1] <= 512 and wp.shape[-1] <= 1024:
             total = total + _InterLevel.apply(c, w, cp, wp, widths[i])     # the same arithmetic as one HIP launch
             continue
         knots, vals = blur_stepfun(c, pdf, widths[i])
