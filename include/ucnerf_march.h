@@ -254,6 +254,11 @@ int ucn_cast_probe_tdist(const float *tdist, const float *origins, const float *
  * contracted mean / 2 [B,3], contracted std / 2 [B]. */
 int ucn_contract_probe(const float *means, const float *stds, uint32_t B, float *out_mean, float *out_std,
                        ucn_stream_t stream);
+/* The level groups ucn_march_features forms for the grid of `f` (host only, nothing is launched): a thread of group g
+ * computes levels_out[first_out[g]] ... levels_out[first_out[g + 1] - 1], in that order.  layout: as there (only
+ * UCN_RAYS_INCOHERENT matters: such launches keep the coarse levels in a group of their own).  levels_out: HOST [num_levels],
+ * first_out: HOST [num_levels + 1].  Returns the number of groups, or -1 on a bad argument. */
+int ucn_level_groups_probe(const ucn_field_t *f, uint32_t levels_per_block, int layout, uint32_t *levels_out, uint32_t *first_out);
 
 /* Same featurisation for caller-supplied Gaussians (ref: models.py:485-512 predict_density as
  * called by extract.py:56-57,96): means [B,G,3], stds [B,G]; warp=0 skips the contraction. */

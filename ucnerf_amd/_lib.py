@@ -78,6 +78,7 @@ SIGNATURES = {
     "ucn_s_to_t": [c_vp, c_vp, c_vp, c_u32, c_u32, c_i32, c_f32, c_vp, c_vp],
     "ucn_march_features": [ctypes.POINTER(UcnField), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32,
                            c_u32, c_u32, c_u32, c_i32, c_vp, c_vp, c_vp, c_vp],
+    "ucn_level_groups_probe": [ctypes.POINTER(UcnField), c_u32, c_i32, c_vp, c_vp],
     "ucn_march_features_backward": [ctypes.POINTER(UcnField), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                     c_f32, c_u32, c_u32, c_u32, c_i32, c_vp, c_vp, c_vp, c_vp],
     "ucn_march_features_tdist": [ctypes.POINTER(UcnField), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_u32, c_u32, c_u32,
@@ -179,6 +180,10 @@ _RESTYPES = {"ucn_last_error": ctypes.c_char_p, "ucn_abi_version": c_u32, "ucn_f
              "ucn_prop_train_bwd_ws_floats": c_u64, "ucn_sky_train_packed_bytes": c_u64, "ucn_wgrad_ws_floats": c_u64, "ucn_wgrad_f32_ws_floats": c_u64, "ucn_wgrad_h3_ws_floats": c_u64, "ucn_pack_h3_bytes": c_u64, "ucn_relu_bits_words": c_u64, "ucn_marching_cubes_ws_bytes": c_u64, "ucn_image_metrics_ws_bytes": c_u64, "ucn_sky_train_act_ld": c_u32,
              "ucn_sky_train_grad_ld": c_u32}
 
+# Entry points added without an ABI bump: host-side probes that no product path calls.  An older build of the same ABI
+# loaded through UCN_LIB_PATH may lack them; every other symbol is required.
+_ADDED_WITHIN_ABI = {"ucn_level_groups_probe"}
+
 _lib = None
 
 
@@ -193,6 +198,8 @@ def load():
             "ucnerf_amd has no CPU / eager fallback.")
     lib = ctypes.CDLL(LIB_PATH)
     for name, args in SIGNATURES.items():
+        if name in _ADDED_WITHIN_ABI and not hasattr(lib, name):
+            continue                     # an earlier build of the same ABI (UCN_LIB_PATH, A/B measurements)
         fn = getattr(lib, name)          # AttributeError = header/library mismatch: fail loudly
         fn.argtypes = args
         fn.restype = _RESTYPES.get(name, ctypes.c_int)

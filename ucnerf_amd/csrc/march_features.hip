@@ -13,10 +13,13 @@
 // cast / contraction probes.  The sample geometry is grid_cast.h, the lattice addressing grid_rows.h -- both shared with the
 // table gradient (march_features_bwd.hip); the scale planes are march_scale.hip.
 //
-// Mapping (CDNA4): one thread = one sample x `levels_per_block` consecutive levels; blockIdx.y is
-// the level group, so the grid is level-major in dispatch order and an XCD's L2 (4 MiB) sees one
-// 4 MiB hashed level slice at a time (measured: levels_per_block 1 -> 16 costs 1.8x); lanes of a wave
-// are consecutive samples of a ray -> the [L][B][C] store is a contiguous 64*C*4-byte run per wave.
+// Mapping (CDNA4): one thread = one sample x one GROUP of levels (make_groups); blockIdx.y is the group, so the grid is
+// level-major in dispatch order.  Auto grouping: every fine level (resolution > 2048) is a group of its own, so an XCD's L2
+// (4 MiB) sees one 4 MiB hashed level slice at a time (measured: all 16 levels per thread costs 1.8x), and the coarse levels are
+// dealt out over those groups -- config B: one coarse level per fine level, the coarsest with the finest -- instead of forming a
+// VALU-bound group of their own that derives the sample geometry a ninth time (1.104 -> 1.042 ms per 10 240-ray pass,
+// profiles/level_pairs/).  Lanes of a wave are neighbouring rays at one sample index (layout 2) or consecutive samples of a ray
+// -> the [L][B][C] store is a contiguous 64*C*4-byte run per wave.
 //
 // What bounds it (rocprofv3, r01b): with the tables L2/MALL-resident the kernel is VALU-bound
 // (SQ_ACTIVE_INST_VALU = 21 % of wave-cycles at 4 waves/SIMD = 84 % of a SIMD), ~3000 VALU
@@ -279,14 +282,35 @@ constexpr uint32_t kSharedCellMaxRes = 64;                          // dense lev
 // kSharedCellMaxRes
 constexpr uint32_t kLanePairMinRes = 2048u;
 
+// The thread's levels are level_of(i0) ... level_of(i1 - 1), in that order (level_of: wave-uniform index -> level).
 // layout: 0 = [L][B][C] (b as given), 1 = [B][L*C]
-template <uint32_t C, typename TT>
-__device__ __forceinline__ void featurise(const UcnLevels &lvls, const TT *__restrict__ table, uint32_t lvl0,
-                                          uint32_t lvl1, const float (&u)[6][3], const float (&rs)[6], uint32_t G,
+template <uint32_t C, typename TT, typename LevelOf>
+__device__ __forceinline__ void featurise(const UcnLevels &lvls, const TT *__restrict__ table, LevelOf level_of, uint32_t i0,
+                                          uint32_t i1, const float (&u)[6][3], const float (&rs)[6], uint32_t G,
                                           size_t B, size_t b, float *__restrict__ out, bool sample_major, bool out_bf16 = false,
                                           bool full_wave = false, uint32_t lp_min_res = kLanePairMinRes) {
     const uint32_t F_out = lvls.L * C;
-    for (uint32_t lvl = lvl0; lvl < lvl1; lvl++) {
+    const auto store = [&](uint32_t lvl, const float (&acc)[C]) {
+        float *o = sample_major ? out + b * F_out + (size_t)lvl * C : out + ((size_t)lvl * B + b) * C;
+        const float inv = (float)G;
+        if constexpr (C == 2) {
+            if (out_bf16) {            // [L][B] pairs of bf16 (round to nearest even): what the bf16 MLP would make of the floats
+                typedef float f2v __attribute__((ext_vector_type(2)));
+                typedef __bf16 bf2v __attribute__((ext_vector_type(2)));
+                const f2v t = {acc[0] / inv, acc[1] / inv};
+                reinterpret_cast<uint32_t *>(out)[(size_t)lvl * B + b] = __builtin_bit_cast(uint32_t, __builtin_convertvector(t, bf2v));
+                return;
+            }
+            *reinterpret_cast<float2 *>(o) = make_float2(acc[0] / inv, acc[1] / inv);
+        } else if constexpr (C == 4) {
+            *reinterpret_cast<float4 *>(o) = make_float4(acc[0] / inv, acc[1] / inv, acc[2] / inv, acc[3] / inv);
+        } else {
+#pragma unroll
+            for (uint32_t c = 0; c < C; c++) o[c] = acc[c] / inv;
+        }
+    };
+    for (uint32_t i = i0; i < i1; i++) {
+        const uint32_t lvl = level_of(i);
         const UcnLevel lv = lvls.lv[lvl];
         const TT *tab = table + (size_t)lv.first_row * C;
         float acc[C];
@@ -320,23 +344,7 @@ __device__ __forceinline__ void featurise(const UcnLevels &lvls, const TT *__res
                 else level_accumulate<C, false, false>(lv, tab, u, rs, G, acc);
             }
         }
-        float *o = sample_major ? out + b * F_out + (size_t)lvl * C : out + ((size_t)lvl * B + b) * C;
-        const float inv = (float)G;
-        if constexpr (C == 2) {
-            if (out_bf16) {            // [L][B] pairs of bf16 (round to nearest even): what the bf16 MLP would make of the floats
-                typedef float f2v __attribute__((ext_vector_type(2)));
-                typedef __bf16 bf2v __attribute__((ext_vector_type(2)));
-                const f2v t = {acc[0] / inv, acc[1] / inv};
-                reinterpret_cast<uint32_t *>(out)[(size_t)lvl * B + b] = __builtin_bit_cast(uint32_t, __builtin_convertvector(t, bf2v));
-                continue;
-            }
-            *reinterpret_cast<float2 *>(o) = make_float2(acc[0] / inv, acc[1] / inv);
-        } else if constexpr (C == 4) {
-            *reinterpret_cast<float4 *>(o) = make_float4(acc[0] / inv, acc[1] / inv, acc[2] / inv, acc[3] / inv);
-        } else {
-#pragma unroll
-            for (uint32_t c = 0; c < C; c++) o[c] = acc[c] / inv;
-        }
+        store(lvl, acc);
     }
 }
 
@@ -363,30 +371,65 @@ __global__ __launch_bounds__(256) void k_contract_probe(const float *__restrict_
     out_std[b] = sd;
 }
 
-// Levels handled by one thread: group g = levels [lo[g], lo[g+1]).  A thread re-derives the sample's six
-// contracted positions (~800 VALU instructions) once per GROUP, then pays ~400-500 per level.  Fine
-// hashed levels stay alone (level-major dispatch keeps one 4 MiB slice per XCD L2); the coarse levels,
-// which are VALU-bound and whose accesses are concentrated on a few cells, share the geometry.
-struct LevelGroups {
-    uint8_t lo[UCN_MAX_LEVELS + 1];
+// Levels handled by one thread: group g = list[lo[g]] ... list[lo[g+1] - 1], in that order.  A thread re-derives the
+// sample's six contracted positions (~800 VALU instructions) once per GROUP, then pays ~400-500 per level.
+//
+// levels_per_block = k > 0: contiguous groups of k levels.
+// Auto (0): a level is COARSE up to resolution 2048 and FINE above.  Every fine level is a group of its own -- level-major dispatch
+// keeps its 4 MiB slice in an XCD's L2.  Rendering (a wave's rays are neighbouring pixels): the coarse levels run at their VALU
+// floor while the fine ones are bound by the texture-data return path with VALU 56 % busy, so the coarse levels are dealt out over
+// the fine groups.  A thread runs its levels one after the other; what the pairing saves is the group that derived the geometry
+// a ninth time, and what overlap there is comes from the other waves of the SIMD.  UCN_RAYS_INCOHERENT (random training rays: the
+// coarse hashed levels share no lines and are themselves memory-bound) and grids with only one kind of level keep contiguous
+// groups, the coarse levels eight together: pairing cost +25 % there (profiles/level_pairs/after.txt).
+struct LevelGroups {                 // whole words: a kernel reads them from its arguments with scalar loads (bytes would go through the vector path)
+    uint32_t lo[UCN_MAX_LEVELS + 1];
+    uint32_t list[UCN_MAX_LEVELS];
     uint32_t n;
 };
-static LevelGroups make_groups(const UcnLevels &lv, uint32_t levels_per_block) {
+static LevelGroups make_groups(const UcnLevels &lv, uint32_t levels_per_block, bool incoherent) {
     LevelGroups g;
     g.n = 0;
-    uint32_t l = 0;
     const uint32_t cres = 2048u, cgrp = 8u;   // measured: (512..8192) x (3..8) all within 3 %; this is the best
-    while (l < lv.L) {
-        g.lo[g.n++] = (uint8_t)l;
-        uint32_t take = levels_per_block;
-        if (levels_per_block == 0) take = lv.lv[l].resolution <= cres ? cgrp : 1u;          // auto
-        uint32_t end = l + take < lv.L ? l + take : lv.L;
-        if (levels_per_block == 0)                                                        // a group never mixes coarse and fine
-            for (uint32_t k = l + 1; k < end; k++)
-                if (lv.lv[k].resolution > cres) { end = k; break; }
-        l = end;
+    uint32_t coarse[UCN_MAX_LEVELS], fine[UCN_MAX_LEVELS], nc = 0, nf = 0;   // each in level order = ascending resolution
+    for (uint32_t l = 0; l < lv.L; l++) {
+        if (lv.lv[l].resolution <= cres) coarse[nc++] = l;
+        else fine[nf++] = l;
     }
-    g.lo[g.n] = (uint8_t)lv.L;
+    if (levels_per_block != 0 || nc == 0 || nf == 0 || incoherent) {
+        for (uint32_t l = 0; l < lv.L; l++) g.list[l] = l;
+        uint32_t l = 0;
+        while (l < lv.L) {
+            g.lo[g.n++] = l;
+            const uint32_t take = levels_per_block ? levels_per_block : (lv.lv[l].resolution <= cres ? cgrp : 1u);
+            uint32_t end = l + take < lv.L ? l + take : lv.L;
+            if (levels_per_block == 0)                                                    // a group never mixes coarse and fine
+                for (uint32_t k = l + 1; k < end; k++)
+                    if (lv.lv[k].resolution > cres) { end = k; break; }
+            l = end;
+        }
+        g.lo[g.n] = lv.L;
+        return g;
+    }
+    // nc coarse levels over nf fine groups: nc / nf each, the remainder to the lowest-resolution (lightest) fine levels; a
+    // group holds at most cgrp levels, what does not fit stays in coarse-only groups behind the fine ones
+    uint32_t per = nc / nf, extra = nc % nf;
+    if (per >= cgrp - 1u) { per = cgrp - 1u; extra = 0; }
+    // Which coarse level with which fine level (profiles/level_pairs/assignments.txt): the fine groups ascend in resolution and take
+    // the coarse levels from the top, so the coarsest levels (dense, one shared cell per sample: the least traffic) ride with the
+    // finest, most return-path-bound levels.  A thread runs its coarse levels first, its fine level last.
+    uint32_t c_hi = nc, n = 0;                                       // coarse[0 .. c_hi) are still to be placed
+    for (uint32_t i = 0; i < nf; i++) {
+        g.lo[g.n++] = n;
+        const uint32_t cnt = per + (i < extra ? 1u : 0u);
+        for (uint32_t k = 0; k < cnt; k++) g.list[n++] = coarse[--c_hi];
+        g.list[n++] = fine[i];
+    }
+    for (uint32_t c_lo = 0; c_lo < c_hi;) {
+        g.lo[g.n++] = n;
+        for (uint32_t k = 0; k < cgrp && c_lo < c_hi; k++) g.list[n++] = coarse[c_lo++];
+    }
+    g.lo[g.n] = n;
     return g;
 }
 
@@ -416,11 +459,12 @@ __device__ __forceinline__ void march_features_body(const UcnLevels &lvls, const
     else { ray = (uint32_t)(b / S); s = (uint32_t)(b - (size_t)ray * S); }
     float u[6][3], rs[6], csum[3], tsum;
     cast_sample<TD>(in, hx, std_scale, ray, s, S, u, rs, csum, tsum);
-    const uint32_t lvl0 = grp.lo[blockIdx.y], lvl1 = grp.lo[blockIdx.y + 1];
+    const uint32_t i0 = grp.lo[blockIdx.y], i1 = grp.lo[blockIdx.y + 1];
+    const auto level_of = [&grp](uint32_t i) -> uint32_t { return grp.list[i]; };
     const bool full_wave = __ballot(true) == ~0ull;                  // the lane-paired fetch trades rows between lanes i and i + 32
     const uint32_t lp_min = (layout & 0x20) ? kSharedCellMaxRes : kLanePairMinRes;     // 0x20: UCN_RAYS_INCOHERENT (private bit)
-    if constexpr (sizeof(TT) == 2) featurise<C, TT>(lvls, table, lvl0, lvl1, u, rs, 6, B, b, features, (layout & 3) == 1, (layout & 0x10) != 0, full_wave, lp_min);
-    else featurise<C, TT>(lvls, table, lvl0, lvl1, u, rs, 6, B, b, features, (layout & 3) == 1, false, full_wave, lp_min);
+    if constexpr (sizeof(TT) == 2) featurise<C, TT>(lvls, table, level_of, i0, i1, u, rs, 6, B, b, features, (layout & 3) == 1, (layout & 0x10) != 0, full_wave, lp_min);
+    else featurise<C, TT>(lvls, table, level_of, i0, i1, u, rs, 6, B, b, features, (layout & 3) == 1, false, full_wave, lp_min);
     if (blockIdx.y == 0) {
         const size_t o = (size_t)ray * S + s;                     // per-sample side outputs stay [N,S]
         if (coord_out) {
@@ -471,7 +515,7 @@ __global__ __launch_bounds__(256) void k_points_features(UcnLevels lvls, const f
     }
     const uint32_t lvl0 = blockIdx.y * lpb;
     const uint32_t lvl1 = lvl0 + lpb < lvls.L ? lvl0 + lpb : lvls.L;
-    featurise<C, float>(lvls, table, lvl0, lvl1, u, rs, G, Bn, b, features, false);
+    featurise<C, float>(lvls, table, [](uint32_t i) -> uint32_t { return i; }, lvl0, lvl1, u, rs, G, Bn, b, features, false);
     if (blockIdx.y == 0 && coord_out) {
         coord_out[b * 3 + 0] = cs0 / (float)G; coord_out[b * 3 + 1] = cs1 / (float)G; coord_out[b * 3 + 2] = cs2 / (float)G;
     }
@@ -502,7 +546,7 @@ static int march_features_launch(const ucn_field_t *f, const RayInputs &in, floa
     if (N == 0) return 0;
     const size_t B = (size_t)N * S;
     UCN_REQUIRE(B <= 0xFFFFFF00ull, "march_features: too many samples in one call (%zu)", B);
-    const LevelGroups grp = make_groups(lv, levels_per_block);
+    const LevelGroups grp = make_groups(lv, levels_per_block, incoherent);
     const HexPattern hx = make_hex();
     hipStream_t st = (hipStream_t)stream;
     // co-resident shape: 512 threads = two waves per SIMD, 88 KiB of LDS reserved -> ONE such workgroup per CU, and
@@ -594,6 +638,19 @@ extern "C" int ucn_contract_probe(const float *means, const float *stds, uint32_
                        out_std);
     UCN_LAUNCH_CHECK("contract_probe");
     return 0;
+}
+
+/* The level groups of ucn_march_features for this grid (host only, no launch): group g = levels_out[first_out[g]] ...
+ * levels_out[first_out[g + 1] - 1] in the thread's order; layout: only UCN_RAYS_INCOHERENT is looked at; levels_out [num_levels], first_out [num_levels + 1];
+ * returns the number of groups, or -1 on a bad argument. */
+extern "C" int ucn_level_groups_probe(const ucn_field_t *f, uint32_t levels_per_block, int layout, uint32_t *levels_out,
+                                      uint32_t *first_out) {
+    UcnLevels lv;
+    if (!levels_out || !first_out || field_levels(f, &lv)) return -1;
+    const LevelGroups grp = make_groups(lv, levels_per_block, (layout & UCN_RAYS_INCOHERENT) != 0);
+    for (uint32_t i = 0; i < lv.L; i++) levels_out[i] = grp.list[i];
+    for (uint32_t g = 0; g <= grp.n; g++) first_out[g] = grp.lo[g];
+    return (int)grp.n;
 }
 
 extern "C" int ucn_points_features(const ucn_field_t *f, const float *means, const float *stds, uint32_t B, uint32_t G,

@@ -522,7 +522,7 @@ class Model(nn.Module):
     max_chunk_rays: int = 10240          # rays per internal pass.  At S=128, F=32 the feature workspace is 168 MB: with
     #                                      the tables (64 + 24 MB) it stays inside the 256 MB Infinity Cache between the
     #                                      featurisation that writes it and the MLP that reads it (65 536: 5 % slower)
-    levels_per_block: int = 0            # hash-grid levels per thread: 0 = auto (coarse levels together, fine alone)
+    levels_per_block: int = 0            # hash-grid levels per thread: 0 = auto (every fine level its own group, the coarse levels dealt out over them)
     overlap_streams: bool = False        # featurisation of pass i+1 beside the MLP of pass i on a second HIP stream:
     #                                      measured +1 % only (both kernels want every CU), so off by default
     rays_fastest: bool = True            # wave lanes = neighbouring rays at one sample index (L1/L2 locality)
