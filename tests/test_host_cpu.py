@@ -493,7 +493,7 @@ def test_data_loss_levels_and_lazy_stats():
 
 def test_hash_decay_on_host_tensors_is_the_reference_reduction():
     """models.py:297-306: mean over (level, channel) of the per-level mean of embeddings^2 -- the host-tensor form of
-    train_graph.hash_decay (the device form is ucn_hash_decay, pinned by the G10 loss values)."""
+    train_graph.hash_decay (the device form is ucn_hash_decay: tests/test_train_tail_gpu.py holds it to float64, both ways)."""
     from ucnerf_amd.internal import configs, models, train_graph
     with models.bindings(NerfMLP=dict(grid_log2_hashmap_size=10), PropMLP=dict(grid_log2_hashmap_size=10)):
         model = models.Model(config=configs.Config(), num_levels=2)

@@ -334,7 +334,7 @@ def compute_data_loss(batch, renderings, config):
     coarse = getattr(config, 'data_coarse_loss_mult', 0.)
     levels = [r['rgb'] for r in renderings]
     if (n_lvl <= 4 and target.shape[-1] == 3 and _f32_cuda(target, *levels) and all(l.numel() == target.numel() for l in levels)
-            and batch['lossmult'].numel() * 3 == target.numel()):
+            and batch['lossmult'].numel() * 3 == target.numel() and target.numel() > 0):
         # the whole function as ONE HIP node (csrc/heads_train.hip): weighted loss + the mse statistics
         N = target.numel() // 3
         mult = None if getattr(config, 'disable_multiscale_loss', False) else batch['lossmult'].reshape(N).float().contiguous()
@@ -425,7 +425,8 @@ def hash_decay_loss(ray_history, config):
 
 def sky_loss(batch, renderings):
     """ref train_utils.py:149-157."""
-    if len(renderings) <= 4 and all('acc' in r for r in renderings) and _f32_cuda(batch['sky_segs'], *[r['acc'] for r in renderings]):
+    if (len(renderings) <= 4 and all('acc' in r for r in renderings) and _f32_cuda(batch['sky_segs'], *[r['acc'] for r in renderings])
+            and batch['sky_segs'].numel() > 0):
         # one HIP node for all levels (csrc/heads_train.hip); `acc` IS the sum of the level's weights (render.py:199)
         N = batch['sky_segs'].numel()
         return _SkyLoss.apply(batch['sky_segs'].reshape(N).contiguous(), *[r['acc'].reshape(N) for r in renderings])
@@ -442,7 +443,7 @@ def transformIdentityLoss(renderings):
     A = renderings[0]['affine_trans']
     A_sky = renderings[0].get('affine_trans_sky')
     maps = [A] + ([A_sky] if A_sky is not None else [])
-    if _f32_cuda(*maps, half_ok=True) and A.shape[-2:] == (3, 4):
+    if _f32_cuda(*maps, half_ok=True) and A.shape[-2:] == (3, 4) and A.numel() > 0:
         # bf16 maps (the heads ran under train.py:165's autocast) are upcast first: exact, and what `eye (float64) - A` promotes through
         return _IdentityLoss.apply(A.float(), A_sky.float() if A_sky is not None else None)     # one HIP node (csrc/heads_train.hip)
     eye = torch.eye(4, dtype=torch.float64, device=A.device)[:3].unsqueeze(0).expand(A.shape[0], 3, 4)
