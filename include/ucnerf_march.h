@@ -120,6 +120,13 @@ int ucn_resample(const float *sdist_prev /*[N,n_prev+1]*/, const float *weights_
                  uint32_t n_prev, float dilation, float anneal, float resample_padding,
                  const float *u_table, const float *jitter, uint32_t jitter_cols, float max_jitter,
                  uint32_t N, uint32_t S, float *sdist_out /*[N,S+1]*/, ucn_stream_t stream);
+/* ABI 31 (Model.near_anneal_rate, models.py:137-146): the same on the domain [s_near, 1], 0 <= s_near < 1 -- the first level's
+ * interval is [s_near, 1], the dilated knots are clipped to it (stepfun.py:80) and the first fencepost is clamped to s_near
+ * (stepfun.py:290).  ucn_resample is this call with s_near = 0, bit for bit. */
+int ucn_resample_domain(const float *sdist_prev, const float *weights_prev, uint32_t n_prev, float dilation, float anneal,
+                        float resample_padding, float s_near, const float *u_table, const float *jitter,
+                        uint32_t jitter_cols, float max_jitter, uint32_t N, uint32_t S, float *sdist_out,
+                        ucn_stream_t stream);
 
 /* ref: coord.py:137-177 construct_ray_warps + models.py:130,208 (Model.raydist_fn, Model.power_lambda): the metric
  * fenceposts of one level, tdist = fn_inv(sdist * fn(far) + (1 - sdist) * fn(near)) per ray, in fp32 in the reference's
@@ -371,6 +378,21 @@ int ucn_composite_tdist(const float *density, const float *rgbs /*|NULL*/, const
                         const float *far_, const float *directions, float bg_intensity, int opaque_background,
                         uint32_t N, uint32_t S, float *weights_out, float *out_main, float *out_extras,
                         ucn_stream_t stream);
+/* ABI 31: compositing with a per-ray colour gain and a per-ray background colour (models.py:245-269).
+ *   ray_gain [N,3]|NULL  the RawNeRF exposure of the ray (exposure_values, times the learned scaling): the ray composites
+ *                        gain_k * rgbs_ik; rgbs_out [N,S,3]|NULL receives those scaled colours (the reference scales
+ *                        ray_results['rgb'] in place) and MAY BE rgbs itself;
+ *   ray_bg   [N,3]|NULL  replaces the scalar: out_main[k] = sum_i w_i gain_k rgbs_ik + max(1 - acc, 0) * ray_bg[k]; NULL keeps
+ *                        bg_intensity.
+ * With ray_gain = ray_bg = NULL and rgbs_out NULL or == rgbs this launches ucn_composite[_tdist]'s kernel: the same bits. */
+int ucn_composite_rays(const float *density, const float *rgbs /*|NULL*/, const float *sdist, const float *near_,
+                       const float *far_, const float *directions, const float *ray_gain, const float *ray_bg,
+                       float bg_intensity, int opaque_background, uint32_t N, uint32_t S, float *weights_out,
+                       float *out_main, float *out_extras, float *rgbs_out, ucn_stream_t stream);
+int ucn_composite_rays_tdist(const float *density, const float *rgbs /*|NULL*/, const float *tdist, const float *far_,
+                             const float *directions, const float *ray_gain, const float *ray_bg, float bg_intensity,
+                             int opaque_background, uint32_t N, uint32_t S, float *weights_out, float *out_main,
+                             float *out_extras, float *rgbs_out, ucn_stream_t stream);
 
 /* Backward of ucn_composite's differentiable outputs w.r.t. density and rgbs: what autograd derives from
  * render.py:155-174 + :203-216 in the reference's training step (train.py:165-221).  g_weights [N,S]|NULL is the
@@ -386,6 +408,20 @@ int ucn_composite_backward_tdist(const float *density, const float *rgbs, const 
                                  const float *directions, float bg_intensity, int opaque_background, uint32_t N,
                                  uint32_t S, const float *g_weights, const float *g_main, float *g_density,
                                  float *g_rgbs, ucn_stream_t stream);
+/* ABI 31: backward of ucn_composite_rays[_tdist].  rgbs are the UNSCALED colours (the forward's input), g_rgbs their gradient
+ * w_i g_k gain_k; g_gain [N,3]|NULL = g_k sum_i w_i rgbs_ik (one write per ray, no atomics); ray_bg carries no gradient.
+ * g_rgbs_scaled [N,S,3]|NULL: a gradient that arrived on rgbs_out -- g_rgbs_ik += gain_k * it, g_gain_k += sum_i it * rgbs_ik.
+ * With the four new pointers NULL this launches ucn_composite_backward[_tdist]'s kernel: the same bits. */
+int ucn_composite_rays_backward(const float *density, const float *rgbs, const float *sdist, const float *near_,
+                                const float *far_, const float *directions, const float *ray_gain, const float *ray_bg,
+                                float bg_intensity, int opaque_background, uint32_t N, uint32_t S, const float *g_weights,
+                                const float *g_main, const float *g_rgbs_scaled, float *g_density, float *g_rgbs,
+                                float *g_gain /*[N,3]|NULL*/, ucn_stream_t stream);
+int ucn_composite_rays_backward_tdist(const float *density, const float *rgbs, const float *tdist, const float *directions,
+                                      const float *ray_gain, const float *ray_bg, float bg_intensity, int opaque_background,
+                                      uint32_t N, uint32_t S, const float *g_weights, const float *g_main,
+                                      const float *g_rgbs_scaled, float *g_density, float *g_rgbs, float *g_gain,
+                                      ucn_stream_t stream);
 
 /* ------------------------------------------------- training-side reductions + optimiser
  * ucn_adam_step: torch.optim.Adam (amsgrad = False, weight_decay = 0; what train_utils.py:347-366 builds) on one

@@ -11,7 +11,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # UCN_LIB_PATH: another build of the same ABI for A/B measurements; default = the in-tree product
 LIB_PATH = os.environ.get("UCN_LIB_PATH") or os.path.join(_HERE, "csrc", "libucnerf_march.so")
-ABI_VERSION = 30
+ABI_VERSION = 31
 LAUNCH_CORESIDENT = 0x100  # include/ucnerf_march.h UCN_LAUNCH_CORESIDENT
 TABLE_F16 = 0x200
 RAYS_INCOHERENT = 0x1000   # ucn_march_features layout flag: random (training) rays -> lane-paired fetch on every hashed level
@@ -74,6 +74,7 @@ SIGNATURES = {
     "ucn_field_packed_floats": [ctypes.POINTER(UcnField)],
     "ucn_field_pack": [ctypes.POINTER(UcnField), c_vp],
     "ucn_resample": [c_vp, c_vp, c_u32, c_f32, c_f32, c_f32, c_vp, c_vp, c_u32, c_f32, c_u32, c_u32, c_vp, c_vp],
+    "ucn_resample_domain": [c_vp, c_vp, c_u32, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_u32, c_f32, c_u32, c_u32, c_vp, c_vp],
     "ucn_cone_basis": [c_vp, c_vp, c_u32, c_vp, c_vp],
     "ucn_s_to_t": [c_vp, c_vp, c_vp, c_u32, c_u32, c_i32, c_f32, c_vp, c_vp],
     "ucn_march_features": [ctypes.POINTER(UcnField), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32,
@@ -106,11 +107,17 @@ SIGNATURES = {
     "ucn_field_mlp": [ctypes.POINTER(UcnField), c_vp, c_u32, c_u32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp],
     "ucn_composite": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i32, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp],
     "ucn_composite_tdist": [c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i32, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp],
+    "ucn_composite_rays": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i32, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "ucn_composite_rays_tdist": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i32, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp],
     "ucn_tsdf_integrate": [c_vp, c_u32, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_u32, c_f32, c_vp, c_vp, c_vp, c_vp],
     "ucn_compact_alive": [c_vp, c_u32, c_u32, c_i32, c_f32, c_vp, c_vp, c_vp],
     "ucn_field_rgb_compacted": [c_vp, c_vp, c_u32, c_u32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp],
     "ucn_composite_backward": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i32, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp],
     "ucn_composite_backward_tdist": [c_vp, c_vp, c_vp, c_vp, c_f32, c_i32, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "ucn_composite_rays_backward": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i32, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                    c_vp, c_vp],
+    "ucn_composite_rays_backward_tdist": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i32, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                          c_vp],
     "ucn_generate_rays": [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_u32, c_u32, c_u32, c_u32, c_f32, c_f32, c_vp, c_vp, c_vp,
                           c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "ucn_adam_step": [c_vp, c_vp, c_vp, c_vp, c_u64, c_f32, c_f32, c_f32, c_f32, c_u32, c_i32, c_vp],

@@ -83,8 +83,10 @@ __device__ __forceinline__ uint32_t count_from(F f, uint32_t len, float x, uint3
     return lo;
 }
 
+// s_near: the lower end of the domain [s_near, 1] (models.py:137-146 near_anneal_rate; 0 without it): the clip of the dilated
+// knots (stepfun.py:80) and the clamp of the first fencepost (stepfun.py:290).
 __global__ __launch_bounds__(256) void k_resample(const float *__restrict__ sd_prev, const float *__restrict__ w_prev,
-                                                  uint32_t n_prev, float dilation, float anneal, float pad,
+                                                  uint32_t n_prev, float dilation, float anneal, float pad, float s_near,
                                                   const float *__restrict__ u_table, const float *__restrict__ jitter,
                                                   uint32_t jcols, float max_jitter, uint32_t N, uint32_t S,
                                                   float *__restrict__ sd_out) {
@@ -135,7 +137,7 @@ __global__ __launch_bounds__(256) void k_resample(const float *__restrict__ sd_p
                 near = i + 1;
                 pos = i + count_from<false>(A, n + 1, v, i + 2) + count_from<false>(Bq, n, v, i + 2);
             }
-            kn[pos] = fminf(fmaxf(v, 0.0f), 1.0f);
+            kn[pos] = fminf(fmaxf(v, s_near), 1.0f);
             src[pos] = near;
         }
         wave_lds_handoff();
@@ -218,18 +220,18 @@ __global__ __launch_bounds__(256) void k_resample(const float *__restrict__ sd_p
     float *out = sd_out + (size_t)ray * (S + 1);
     for (uint32_t k = lane; k <= S; k += 64) {
         float v;
-        if (k == 0) v = fmaxf(2.0f * c[0] - (c[1] + c[0]) / 2.0f, 0.0f);
+        if (k == 0) v = fmaxf(2.0f * c[0] - (c[1] + c[0]) / 2.0f, s_near);
         else if (k == S) v = fminf(2.0f * c[S - 1] - (c[S - 1] + c[S - 2]) / 2.0f, 1.0f);
         else v = (c[k] + c[k - 1]) / 2.0f;
         out[k] = v;
     }
 }
 
-// First level (n_prev == 0): the step function is the single interval [0, 1] with weight 1, so cdf = [0, 1], the
-// softmax is exactly 1 and every sample is c_k = clamp(u_k, 0, 1) (stepfun.py:283-293 with fp = xp = [0, 1]: the
-// interpolation 0 + fr * (1 - 0) is exact).  One thread per output fencepost.
+// First level (n_prev == 0): the step function is the single interval [s_near, 1] with weight 1, so cdf = [0, 1], the
+// softmax is exactly 1 and every sample is c_k = s_near + clamp(u_k, 0, 1) * (1 - s_near) (stepfun.py:283-293 with xp = [0, 1],
+// fp = [s_near, 1]; at s_near = 0 the interpolation 0 + fr * (1 - 0) is exact).  One thread per output fencepost.
 __global__ __launch_bounds__(256) void k_resample_first(const float *__restrict__ u_table, const float *__restrict__ jitter,
-                                                        uint32_t jcols, float max_jitter, uint32_t N, uint32_t S,
+                                                        uint32_t jcols, float max_jitter, float s_near, uint32_t N, uint32_t S,
                                                         float *__restrict__ sd_out) {
     const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (i >= (uint64_t)N * (S + 1)) return;
@@ -237,10 +239,10 @@ __global__ __launch_bounds__(256) void k_resample_first(const float *__restrict_
     auto cu = [&](uint32_t q) {
         float u = u_table[q];
         if (jitter) u = u + jitter[(size_t)ray * jcols + (jcols > 1 ? q : 0u)] * max_jitter;
-        return fminf(fmaxf(u, 0.0f), 1.0f);
+        return s_near + fminf(fmaxf(u, 0.0f), 1.0f) * (1.0f - s_near);
     };
     float v;
-    if (k == 0) v = fmaxf(2.0f * cu(0) - (cu(1) + cu(0)) / 2.0f, 0.0f);
+    if (k == 0) v = fmaxf(2.0f * cu(0) - (cu(1) + cu(0)) / 2.0f, s_near);
     else if (k == S) v = fminf(2.0f * cu(S - 1) - (cu(S - 1) + cu(S - 2)) / 2.0f, 1.0f);
     else v = (cu(k) + cu(k - 1)) / 2.0f;
     sd_out[i] = v;
@@ -278,16 +280,24 @@ __device__ __forceinline__ float nan_to_num_inf(float v) {
     return v;
 }
 
+// The colours' pointer type: RAY = true may write the scaled colours over the ones it reads (rgbs_out == rgbs), so no __restrict__ there.
+template <bool RAY> struct ColourPtr { typedef const float *__restrict__ type; };
+template <> struct ColourPtr<true> { typedef const float *type; };
+
 // One wave64 per ray, 4 rays per workgroup.  Lane owns CH consecutive samples.
 // TD = false: `sdist` holds normalised fenceposts of the identity curve; TD = true: metric fenceposts (ucn_s_to_t's tdist),
 // near_ unused.  far_ is the batch's metric far either way (the percentile CDF's last fencepost, render.py:234).
-template <int CH, bool TD = false>
-__global__ __launch_bounds__(256) void k_composite(const float *__restrict__ density, const float *__restrict__ rgbs,
+// RAY = true (ucn_composite_rays): each of ray_gain [N,3] (models.py:258-269, the RawNeRF exposure: the ray composites gain_k * c_ik),
+// ray_bg [N,3] (models.py:253-256, replaces the scalar bg) and rgbs_out [N,S,3] (the scaled colours; may be rgbs itself) may be NULL,
+// wave-uniformly.  RAY = false never reads the three and is the kernel of ucn_composite.
+template <int CH, bool TD = false, bool RAY = false>
+__global__ __launch_bounds__(256) void k_composite(const float *__restrict__ density, typename ColourPtr<RAY>::type rgbs,
                                                    const float *__restrict__ sdist, const float *__restrict__ near_,
                                                    const float *__restrict__ far_, const float *__restrict__ dirs,
                                                    float bg, int opaque, uint32_t N, uint32_t S,
                                                    float *__restrict__ weights_out, float *__restrict__ out_main,
-                                                   float *__restrict__ out_extras) {
+                                                   float *__restrict__ out_extras, const float *__restrict__ ray_gain,
+                                                   const float *__restrict__ ray_bg, float *rgbs_out) {
     __shared__ float s_cdf[4][64 * CH + 2];
     __shared__ float s_t[4][64 * CH + 2];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -298,6 +308,9 @@ __global__ __launch_bounds__(256) void k_composite(const float *__restrict__ den
     const float dx = dirs[ray * 3 + 0], dy = dirs[ray * 3 + 1], dz = dirs[ray * 3 + 2];
     const float dnorm = sqrtf((dx * dx + dy * dy) + dz * dz);
     const float *sd = sdist + (size_t)ray * (S + 1);
+    float gn0 = 1.0f, gn1 = 1.0f, gn2 = 1.0f, bg0 = bg, bg1 = bg, bg2 = bg;
+    if (RAY && ray_gain) { gn0 = ray_gain[ray * 3 + 0]; gn1 = ray_gain[ray * 3 + 1]; gn2 = ray_gain[ray * 3 + 2]; }
+    if (RAY && ray_bg) { bg0 = ray_bg[ray * 3 + 0]; bg1 = ray_bg[ray * 3 + 1]; bg2 = ray_bg[ray * 3 + 2]; }
     float tlo[CH], thi[CH], tau[CH];
     float lane_tau = 0.0f;
 #pragma unroll
@@ -334,7 +347,17 @@ __global__ __launch_bounds__(256) void k_composite(const float *__restrict__ den
             const float tm = 0.5f * (tlo[c] + thi[c]);
             if (rgbs) {
                 const float *col = rgbs + ((size_t)ray * S + i) * 3;
-                r += w * col[0]; g += w * col[1]; b += w * col[2];
+                if (RAY) {
+                    float c0 = col[0], c1 = col[1], c2 = col[2];
+                    if (ray_gain) { c0 *= gn0; c1 *= gn1; c2 *= gn2; }
+                    if (rgbs_out && live) {
+                        float *co = rgbs_out + ((size_t)ray * S + i) * 3;
+                        co[0] = c0; co[1] = c1; co[2] = c2;
+                    }
+                    r += w * c0; g += w * c1; b += w * c2;
+                } else {
+                    r += w * col[0]; g += w * col[1]; b += w * col[2];
+                }
             }
             dnum += w * tm;
             lnum += w * logf(tm);
@@ -355,7 +378,7 @@ __global__ __launch_bounds__(256) void k_composite(const float *__restrict__ den
     if (acc < 0.6f) depth = 300.0f;                                  // render.py:208-213
     if (lane == 0 && live) {
         float *o = out_main + (size_t)ray * 5;
-        o[0] = r + bg_w * bg; o[1] = g + bg_w * bg; o[2] = b + bg_w * bg;
+        o[0] = r + bg_w * bg0; o[1] = g + bg_w * bg1; o[2] = b + bg_w * bg2;
         o[3] = depth; o[4] = acc;
     }
     if (!out_extras) return;
@@ -403,13 +426,19 @@ __global__ __launch_bounds__(256) void k_composite(const float *__restrict__ den
 // (the suffix sum is a wave scan).  G collects the direct weight gradient (the losses on `weights`), rgb
 // (sum_i w_i c_i + bg * clamp_min(1 - acc, 0)), acc and depth (clip(nan_to_num(sum_i w_i tm_i / max(acc, eps))), 300
 // where acc < 0.6 -- constant there).
-template <int CH, bool TD = false>
+// RAY = true (ucn_composite_rays_backward): with the per-ray gain the colour term of G_i is sum_k g_k gain_k c_ik and
+// g_rgbs_ik = w_i g_k gain_k (against the UNSCALED colours `rgbs`); with the per-ray background g_bgw = -(g_r bg_r + g_g bg_g + g_b bg_b)
+// under the same clamp; g_gain[ray,k] = g_k sum_i w_i c_ik, one write of 3 floats per ray.  g_hist [N,S,3] is a gradient on the scaled
+// colours the forward returned: g_rgbs_ik += gain_k g_hist_ik, g_gain_k += sum_i g_hist_ik c_ik.  Each of the four may be NULL.
+template <int CH, bool TD = false, bool RAY = false>
 __global__ __launch_bounds__(256) void k_composite_bwd(const float *__restrict__ density, const float *__restrict__ rgbs,
                                                        const float *__restrict__ sdist, const float *__restrict__ near_,
                                                        const float *__restrict__ far_, const float *__restrict__ dirs,
                                                        float bg, int opaque, uint32_t N, uint32_t S,
                                                        const float *__restrict__ g_weights, const float *__restrict__ g_main,
-                                                       float *__restrict__ g_density, float *__restrict__ g_rgbs) {
+                                                       float *__restrict__ g_density, float *__restrict__ g_rgbs,
+                                                       const float *__restrict__ ray_gain, const float *__restrict__ ray_bg,
+                                                       const float *__restrict__ g_hist, float *__restrict__ g_gain) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const uint32_t ray = blockIdx.x * 4u + wv;
     if (ray >= N) return;                                 // wave-uniform, no barriers below
@@ -461,7 +490,17 @@ __global__ __launch_bounds__(256) void k_composite_bwd(const float *__restrict__
                        draw <= t_last;
     const float gd_num = dlive ? gdepth / denom : 0.0f;                                        // d depth / d dnum
     const float gd_acc = dlive && acc >= UCN_EPS ? -gdepth * draw / denom : 0.0f;              // through max(acc, eps)
-    const float g_bgw = (1.0f - acc >= 0.0f) ? -(gr + gg + gb) * bg : 0.0f;                    // clamp_min(1 - acc, 0)
+    float g_bgw = (1.0f - acc >= 0.0f) ? -(gr + gg + gb) * bg : 0.0f;                          // clamp_min(1 - acc, 0)
+    float grg = gr, ggg = gg, gbg = gb;                                                        // g_k gain_k
+    float gn0 = 1.0f, gn1 = 1.0f, gn2 = 1.0f, wc0 = 0.0f, wc1 = 0.0f, wc2 = 0.0f, hc0 = 0.0f, hc1 = 0.0f, hc2 = 0.0f;
+    if (RAY && ray_bg) {
+        const float *pb = ray_bg + (size_t)ray * 3;
+        g_bgw = (1.0f - acc >= 0.0f) ? -((gr * pb[0] + gg * pb[1]) + gb * pb[2]) : 0.0f;
+    }
+    if (RAY && ray_gain) {
+        gn0 = ray_gain[ray * 3 + 0]; gn1 = ray_gain[ray * 3 + 1]; gn2 = ray_gain[ray * 3 + 2];
+        grg = gr * gn0; ggg = gg * gn1; gbg = gb * gn2;
+    }
     float G[CH], lane_p = 0.0f;
 #pragma unroll
     for (int c = 0; c < CH; c++) {
@@ -472,12 +511,29 @@ __global__ __launch_bounds__(256) void k_composite_bwd(const float *__restrict__
             if (g_weights) g += g_weights[(size_t)ray * S + i];
             if (rgbs) {
                 const float *col = rgbs + ((size_t)ray * S + i) * 3;
-                g += (gr * col[0] + gg * col[1]) + gb * col[2];
+                g += (grg * col[0] + ggg * col[1]) + gbg * col[2];
                 float *o = g_rgbs + ((size_t)ray * S + i) * 3;
-                o[0] = w[c] * gr; o[1] = w[c] * gg; o[2] = w[c] * gb;
+                float o0 = w[c] * grg, o1 = w[c] * ggg, o2 = w[c] * gbg;
+                if (RAY) {
+                    wc0 += w[c] * col[0]; wc1 += w[c] * col[1]; wc2 += w[c] * col[2];
+                    if (g_hist) {
+                        const float *gh = g_hist + ((size_t)ray * S + i) * 3;
+                        o0 += gn0 * gh[0]; o1 += gn1 * gh[1]; o2 += gn2 * gh[2];
+                        hc0 += gh[0] * col[0]; hc1 += gh[1] * col[1]; hc2 += gh[2] * col[2];
+                    }
+                }
+                o[0] = o0; o[1] = o1; o[2] = o2;
             }
             G[c] = g;
             lane_p += g * w[c];
+        }
+    }
+    if (RAY && g_gain) {                                   // wave-uniform; zeros without colours (a proposal level)
+        wc0 = wave_sum(wc0); wc1 = wave_sum(wc1); wc2 = wave_sum(wc2);
+        hc0 = wave_sum(hc0); hc1 = wave_sum(hc1); hc2 = wave_sum(hc2);
+        if (lane == 0) {
+            float *o = g_gain + (size_t)ray * 3;
+            o[0] = gr * wc0 + hc0; o[1] = gg * wc1 + hc1; o[2] = gb * wc2 + hc2;
         }
     }
     // sum_{i > j} G_i w_i = total - inclusive prefix
@@ -527,10 +583,11 @@ extern "C" int ucn_s_to_t(const float *sdist, const float *near_, const float *f
     return 0;
 }
 
-extern "C" int ucn_resample(const float *sdist_prev, const float *weights_prev, uint32_t n_prev, float dilation,
-                            float anneal, float resample_padding, const float *u_table, const float *jitter,
-                            uint32_t jitter_cols, float max_jitter, uint32_t N, uint32_t S, float *sdist_out,
-                            ucn_stream_t stream) {
+extern "C" int ucn_resample_domain(const float *sdist_prev, const float *weights_prev, uint32_t n_prev, float dilation,
+                                   float anneal, float resample_padding, float s_near, const float *u_table,
+                                   const float *jitter, uint32_t jitter_cols, float max_jitter, uint32_t N, uint32_t S,
+                                   float *sdist_out, ucn_stream_t stream) {
+    UCN_REQUIRE(s_near >= 0.0f && s_near < 1.0f, "resample: s_near must be in [0, 1), got %g", (double)s_near);
     UCN_REQUIRE(S > 1, "num_samples must be > 1, is %u.", S);                      // stepfun.py:271-272
     UCN_REQUIRE(N == 0 || (u_table && sdist_out), "resample: null pointer argument");
     UCN_REQUIRE(N == 0 || n_prev == 0 || (sdist_prev && weights_prev), "resample: previous level missing");
@@ -540,16 +597,24 @@ extern "C" int ucn_resample(const float *sdist_prev, const float *weights_prev, 
     UCN_REQUIRE(S <= 1024, "resample: at most 1024 samples per ray are supported, got %u", S);
     if (n_prev == 0) {
         hipLaunchKernelGGL(k_resample_first, dim3((uint32_t)(((uint64_t)N * (S + 1) + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                           u_table, jitter, jitter_cols, max_jitter, N, S, sdist_out);
+                           u_table, jitter, jitter_cols, max_jitter, s_near, N, S, sdist_out);
         UCN_LAUNCH_CHECK("resample (first level)");
         return 0;
     }
     const uint32_t m = 3 * n_prev + 1;
     const size_t lds = 4 * sizeof(float) * ((size_t)(n_prev + 1) + n_prev + (m + 1) + m + (m + 1) + S);
     hipLaunchKernelGGL(k_resample, dim3(ucn_div_up(N, 4)), dim3(256), lds, (hipStream_t)stream, sdist_prev, weights_prev, n_prev,
-                       dilation, anneal, resample_padding, u_table, jitter, jitter_cols, max_jitter, N, S, sdist_out);
+                       dilation, anneal, resample_padding, s_near, u_table, jitter, jitter_cols, max_jitter, N, S, sdist_out);
     UCN_LAUNCH_CHECK("resample");
     return 0;
+}
+
+extern "C" int ucn_resample(const float *sdist_prev, const float *weights_prev, uint32_t n_prev, float dilation,
+                            float anneal, float resample_padding, const float *u_table, const float *jitter,
+                            uint32_t jitter_cols, float max_jitter, uint32_t N, uint32_t S, float *sdist_out,
+                            ucn_stream_t stream) {
+    return ucn_resample_domain(sdist_prev, weights_prev, n_prev, dilation, anneal, resample_padding, 0.0f, u_table, jitter,
+                               jitter_cols, max_jitter, N, S, sdist_out, stream);
 }
 
 extern "C" int ucn_cone_basis(const float *cam_dirs, const float *rand_vec, uint32_t N, float *basis_out,
@@ -564,7 +629,8 @@ extern "C" int ucn_cone_basis(const float *cam_dirs, const float *rand_vec, uint
 template <bool TD>
 static int composite_launch(const float *density, const float *rgbs, const float *sdist, const float *near_, const float *far_,
                             const float *directions, float bg_intensity, int opaque_background, uint32_t N, uint32_t S,
-                            float *weights_out, float *out_main, float *out_extras, ucn_stream_t stream) {
+                            float *weights_out, float *out_main, float *out_extras, ucn_stream_t stream,
+                            const float *ray_gain = nullptr, const float *ray_bg = nullptr, float *rgbs_out = nullptr) {
     UCN_REQUIRE(N == 0 || (density && sdist && (TD || near_) && far_ && directions && weights_out && out_main),
                 "composite: null pointer argument");
     UCN_REQUIRE(S >= 1 && S <= 512, "composite: samples per ray must be in [1,512], got %u", S);
@@ -572,8 +638,19 @@ static int composite_launch(const float *density, const float *rgbs, const float
     const dim3 grid(ucn_div_up(N, 4));
     hipStream_t st = (hipStream_t)stream;
 #define UCN_CP(CH)                                                                                                   \
-    hipLaunchKernelGGL((k_composite<CH, TD>), grid, dim3(256), 0, st, density, rgbs, sdist, near_, far_, directions, \
-                       bg_intensity, opaque_background, N, S, weights_out, out_main, out_extras)
+    do {                                                                                                             \
+        if (rays)                                                                                                    \
+            hipLaunchKernelGGL((k_composite<CH, TD, true>), grid, dim3(256), 0, st, density, rgbs, sdist, near_, far_, \
+                               directions, bg_intensity, opaque_background, N, S, weights_out, out_main, out_extras,  \
+                               ray_gain, ray_bg, rgbs_out);                                                          \
+        else                                                                                                         \
+            hipLaunchKernelGGL((k_composite<CH, TD, false>), grid, dim3(256), 0, st, density, rgbs, sdist, near_, far_, \
+                               directions, bg_intensity, opaque_background, N, S, weights_out, out_main, out_extras,  \
+                               nullptr, nullptr, nullptr);                                                           \
+    } while (0)
+    // the per-ray kernel only where it has something to do: a gain or a background, or colours to copy to another buffer
+    const bool rays = ray_gain || ray_bg || (rgbs_out && rgbs_out != rgbs);
+    UCN_REQUIRE(!rgbs_out || rgbs, "composite: rgbs_out without rgbs");
     if (S <= 64) UCN_CP(1);
     else if (S <= 128) UCN_CP(2);
     else if (S <= 256) UCN_CP(4);
@@ -596,6 +673,22 @@ extern "C" int ucn_composite_tdist(const float *density, const float *rgbs, cons
                                    float *weights_out, float *out_main, float *out_extras, ucn_stream_t stream) {
     return composite_launch<true>(density, rgbs, tdist, nullptr, far_, directions, bg_intensity, opaque_background, N, S,
                                   weights_out, out_main, out_extras, stream);
+}
+
+extern "C" int ucn_composite_rays(const float *density, const float *rgbs, const float *sdist, const float *near_,
+                                  const float *far_, const float *directions, const float *ray_gain, const float *ray_bg,
+                                  float bg_intensity, int opaque_background, uint32_t N, uint32_t S, float *weights_out,
+                                  float *out_main, float *out_extras, float *rgbs_out, ucn_stream_t stream) {
+    return composite_launch<false>(density, rgbs, sdist, near_, far_, directions, bg_intensity, opaque_background, N, S,
+                                   weights_out, out_main, out_extras, stream, ray_gain, ray_bg, rgbs_out);
+}
+
+extern "C" int ucn_composite_rays_tdist(const float *density, const float *rgbs, const float *tdist, const float *far_,
+                                        const float *directions, const float *ray_gain, const float *ray_bg,
+                                        float bg_intensity, int opaque_background, uint32_t N, uint32_t S, float *weights_out,
+                                        float *out_main, float *out_extras, float *rgbs_out, ucn_stream_t stream) {
+    return composite_launch<true>(density, rgbs, tdist, nullptr, far_, directions, bg_intensity, opaque_background, N, S,
+                                  weights_out, out_main, out_extras, stream, ray_gain, ray_bg, rgbs_out);
 }
 
 namespace {
@@ -669,7 +762,8 @@ template <bool TD>
 static int composite_backward_launch(const float *density, const float *rgbs, const float *sdist, const float *near_,
                                      const float *far_, const float *directions, float bg_intensity, int opaque_background,
                                      uint32_t N, uint32_t S, const float *g_weights, const float *g_main, float *g_density,
-                                     float *g_rgbs, ucn_stream_t stream) {
+                                     float *g_rgbs, ucn_stream_t stream, const float *ray_gain = nullptr,
+                                     const float *ray_bg = nullptr, const float *g_hist = nullptr, float *g_gain = nullptr) {
     UCN_REQUIRE(N == 0 || (density && sdist && (TD || (near_ && far_)) && directions && g_main && g_density),
                 "composite_backward: null pointer argument");
     UCN_REQUIRE((rgbs == nullptr) == (g_rgbs == nullptr), "composite_backward: rgbs and g_rgbs come together");
@@ -678,8 +772,18 @@ static int composite_backward_launch(const float *density, const float *rgbs, co
     const dim3 grid(ucn_div_up(N, 4));
     hipStream_t st = (hipStream_t)stream;
 #define UCN_CB(CH)                                                                                                     \
-    hipLaunchKernelGGL((k_composite_bwd<CH, TD>), grid, dim3(256), 0, st, density, rgbs, sdist, near_, far_, directions, \
-                       bg_intensity, opaque_background, N, S, g_weights, g_main, g_density, g_rgbs)
+    do {                                                                                                               \
+        if (rays)                                                                                                      \
+            hipLaunchKernelGGL((k_composite_bwd<CH, TD, true>), grid, dim3(256), 0, st, density, rgbs, sdist, near_, far_, \
+                               directions, bg_intensity, opaque_background, N, S, g_weights, g_main, g_density, g_rgbs,  \
+                               ray_gain, ray_bg, g_hist, g_gain);                                                      \
+        else                                                                                                           \
+            hipLaunchKernelGGL((k_composite_bwd<CH, TD, false>), grid, dim3(256), 0, st, density, rgbs, sdist, near_, far_, \
+                               directions, bg_intensity, opaque_background, N, S, g_weights, g_main, g_density, g_rgbs,  \
+                               nullptr, nullptr, nullptr, nullptr);                                                    \
+    } while (0)
+    const bool rays = ray_gain || ray_bg || g_hist || g_gain;
+    UCN_REQUIRE(!g_hist || rgbs, "composite_backward: a gradient on the scaled colours without rgbs");
     if (S <= 64) UCN_CB(1);
     else if (S <= 128) UCN_CB(2);
     else if (S <= 256) UCN_CB(4);
@@ -703,4 +807,22 @@ extern "C" int ucn_composite_backward_tdist(const float *density, const float *r
                                             float *g_rgbs, ucn_stream_t stream) {
     return composite_backward_launch<true>(density, rgbs, tdist, nullptr, nullptr, directions, bg_intensity, opaque_background,
                                            N, S, g_weights, g_main, g_density, g_rgbs, stream);
+}
+
+extern "C" int ucn_composite_rays_backward(const float *density, const float *rgbs, const float *sdist, const float *near_,
+                                           const float *far_, const float *directions, const float *ray_gain,
+                                           const float *ray_bg, float bg_intensity, int opaque_background, uint32_t N,
+                                           uint32_t S, const float *g_weights, const float *g_main, const float *g_rgbs_scaled,
+                                           float *g_density, float *g_rgbs, float *g_gain, ucn_stream_t stream) {
+    return composite_backward_launch<false>(density, rgbs, sdist, near_, far_, directions, bg_intensity, opaque_background, N, S,
+                                            g_weights, g_main, g_density, g_rgbs, stream, ray_gain, ray_bg, g_rgbs_scaled, g_gain);
+}
+
+extern "C" int ucn_composite_rays_backward_tdist(const float *density, const float *rgbs, const float *tdist,
+                                                 const float *directions, const float *ray_gain, const float *ray_bg,
+                                                 float bg_intensity, int opaque_background, uint32_t N, uint32_t S,
+                                                 const float *g_weights, const float *g_main, const float *g_rgbs_scaled,
+                                                 float *g_density, float *g_rgbs, float *g_gain, ucn_stream_t stream) {
+    return composite_backward_launch<true>(density, rgbs, tdist, nullptr, nullptr, directions, bg_intensity, opaque_background,
+                                           N, S, g_weights, g_main, g_density, g_rgbs, stream, ray_gain, ray_bg, g_rgbs_scaled, g_gain);
 }

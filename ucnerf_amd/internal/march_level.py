@@ -21,7 +21,7 @@ def _f32(t, n, c):
 
 class Rays:
     """The batch as float32 [N, c] tensors, its leading shape `prefix`, and the optional keys that pin the random draws: `rand_vec`
-    [N, 3 * num_levels] and `noise` (batch['march_noise']: per level a dict of 'jitter', 'flip', 'spin'; {} where nothing is pinned)."""
+    [N, 3 * num_levels] and `noise` (batch['march_noise']: per level a dict of 'jitter', 'flip', 'spin', 'bg'; {} where nothing is pinned)."""
     __slots__ = ("o", "d", "vd", "cam", "rad", "near", "far", "prefix", "N", "dev", "rand_vec", "noise")
 
     def __init__(self, batch, num_levels, on_device=True):
@@ -42,16 +42,30 @@ def anneal_of(anneal_slope, train_frac):
     return (anneal_slope * train_frac) / ((anneal_slope - 1) * train_frac + 1) if anneal_slope > 0 else 1.
 
 
-def level_plan(model):
-    """[(i_level, is_prop, S, mlp, dilation)] of models.py:152-168.  dilation = bias + multiplier / (the product of the earlier
-    levels' sample counts); 0.0 with use_dilation off (both knobs <= 0), which ucn_resample reads as "resample undilated"."""
+def s_near_of(model, train_frac):
+    """models.py:137-141: where the rays' normalised interval starts -- 0 without Model.near_anneal_rate, else
+    clip(1 - train_frac / near_anneal_rate, 0, near_anneal_init).  The ONE place that computes it: the level plan's dilation, the
+    first level's interval and the resampling domain (`fenceposts`) read it from here."""
+    rate = getattr(model, 'near_anneal_rate', None)
+    if rate is None:
+        return 0.
+    if train_frac is None:
+        raise ValueError("Model.near_anneal_rate is set: the level plan depends on train_frac")
+    return float(np.clip(1 - train_frac / rate, 0, model.near_anneal_init))
+
+
+def level_plan(model, train_frac=None):
+    """[(i_level, is_prop, S, mlp, dilation)] of models.py:152-168.  dilation = bias + multiplier * (1 - s_near) / (the product of the
+    earlier levels' sample counts), s_near = `s_near_of(model, train_frac)` (0 without near_anneal_rate: train_frac is not read);
+    0.0 with use_dilation off (both knobs <= 0), which ucn_resample reads as "resample undilated"."""
     use_dilation = model.dilation_bias > 0 or model.dilation_multiplier > 0
+    span = 1.0 - s_near_of(model, train_frac)                # init_s_far - init_s_near
     plan, prod_num_samples = [], 1
     for i_level in range(model.num_levels):
         is_prop = i_level < model.num_levels - 1
         S = model.num_prop_samples if is_prop else model.num_nerf_samples
         mlp = model.get_submodule(f'prop_mlp_{i_level}') if is_prop else model.nerf_mlp
-        dilation = model.dilation_bias + model.dilation_multiplier * 1.0 / prod_num_samples if use_dilation else 0.0
+        dilation = model.dilation_bias + model.dilation_multiplier * span / prod_num_samples if use_dilation else 0.0
         if use_dilation and not dilation > 0:
             # (a negative dilation_bias) the reference would dilate by it; ucn_resample takes dilation <= 0 as the UNdilated branch
             raise NotImplementedError(f"dilation {dilation} <= 0 at level {i_level} with use_dilation on: not the shipped configuration")
@@ -74,6 +88,62 @@ def draws(rays, i_level, S, rand, single_jitter):
         spin = _f32(pn['spin'], N, S) if 'spin' in pn else torch.rand(N, S, device=dev)
     rvec = torch.randn(N, 3, device=dev) if rays.rand_vec is None else rays.rand_vec[:, 3 * i_level:3 * i_level + 3].contiguous()
     return jitter, flip, spin, rvec
+
+
+def background(model, rays, i_level, rand):
+    """(bg, ray_bg) of one level (models.py:245-256): the scalar background intensity, and float32 [N, 3] per-ray colours or None.
+    A one-valued Model.bg_intensity_range is that value; a two-valued one is its midpoint for `rand is None` ALONE (models.py:249),
+    else -- `rand = False` included, which is what every evaluation caller of the reference passes: there the reference draws too --
+    one rand(N, 3) * (max - min) + min, drawn AFTER the level's `draws` and its MLP (models.py:256; nothing between them consumes the
+    generator here), so both marches call this behind their dense layers.  With rand = False that is right behind the level's
+    randn(N, 3): jitter, flip and spin are not drawn.  batch['march_noise'][i_level]['bg'] pins the colours (and then consumes
+    nothing of the generator)."""
+    lo, hi = float(model.bg_intensity_range[0]), float(model.bg_intensity_range[1])
+    if lo == hi:
+        return lo, None
+    if rand is None:
+        return (lo + hi) / 2, None
+    pn = rays.noise[i_level]
+    if 'bg' in pn:
+        return lo, _f32(pn['bg'], rays.N, 3)
+    return lo, torch.rand(rays.N, 3, device=rays.dev) * (hi - lo) + lo
+
+
+def ray_gain(model, batch, rays):
+    """models.py:258-269, the RawNeRF exposure: float32 [N, 3] colour gain of every ray, or None without batch['exposure_idx'].
+    gain = exposure_values, times 1 + (exposure_idx > 0) * exposure_scaling_offsets(exposure_idx) with learned_exposure_scaling --
+    plain torch, so autograd carries the compositing node's gradient on it to the embedding."""
+    idx = batch.get('exposure_idx')
+    if idx is None:
+        return None
+    values = batch.get('exposure_values')
+    if values is None:
+        raise TypeError("batch['exposure_idx'] is set but batch['exposure_values'] is None (the reference indexes None here, models.py:261)")
+    N = rays.N
+    gain = values.to(rays.dev).float().reshape(N, -1).expand(N, 3)
+    if model.learned_exposure_scaling:
+        idx = idx.to(rays.dev).reshape(N, -1)[:, 0]
+        scaling = 1 + (idx > 0)[:, None] * model.exposure_scaling_offsets(idx.long())
+        gain = gain * scaling.float()
+    return gain.contiguous()
+
+
+def composite(posts, density, rgbs, dirs, gain, ray_bg, bg, opaque, weights, main, extras, stream):
+    """One compositing launch of a level's N rays: ucn_composite, or ucn_composite_rays with a per-ray gain (the scaled colours are
+    written over `rgbs`, as the reference scales ray_results['rgb'] in place) and / or per-ray background colours."""
+    lib = _lib.load()
+    N, S = density.shape
+    if rgbs is None:
+        gain = None                                            # models.py:584-585: a proposal level's colours are zeros, gain * 0 = 0
+    if gain is None and ray_bg is None:
+        _lib.check(posts.entry(lib, 'ucn_composite')(density.data_ptr(), _lib.ptr(rgbs), *posts.compositing(), dirs.data_ptr(),
+                                                     float(bg), int(bool(opaque)), N, S, weights.data_ptr(), main.data_ptr(),
+                                                     _lib.ptr(extras), stream))
+        return
+    _lib.check(posts.entry(lib, 'ucn_composite_rays')(density.data_ptr(), _lib.ptr(rgbs), *posts.compositing(), dirs.data_ptr(),
+                                                      _lib.ptr(gain), _lib.ptr(ray_bg), float(bg), int(bool(opaque)), N, S,
+                                                      weights.data_ptr(), main.data_ptr(), _lib.ptr(extras),
+                                                      _lib.ptr(rgbs) if gain is not None else None, stream))
 
 
 @functools.lru_cache(maxsize=None)
@@ -112,7 +182,7 @@ class Fenceposts:
         self.sdist, self.near, self.far, self.tdist, self.basis = sdist, near, far, tdist, basis
 
     def entry(self, lib, name):
-        """lib.<name> (ucn_march_features[_backward], ucn_composite[_backward]), or its `_tdist` sibling on metric fenceposts."""
+        """lib.<name> (ucn_march_features[_backward], ucn_composite[_rays][_backward]), or its `_tdist` sibling on metric fenceposts."""
         return getattr(lib, name if self.tdist is None else name + '_tdist')
 
     def geometry(self, rays, flip, spin, sl=slice(None)):
@@ -143,9 +213,13 @@ def fenceposts(model, rays, i_level, S, dilation, train_frac, rand, prev, weight
     basis = torch.empty(N, 6, device=dev)
     sdist_prev, n_prev = (None, 0) if prev is None else (prev.sdist, prev.sdist.shape[1] - 1)
     wp = None if weights_prev is None else weights_prev.detach().contiguous()
-    _lib.check(lib.ucn_resample(_lib.ptr(sdist_prev), _lib.ptr(wp), n_prev, dilation, anneal_of(model.anneal_slope, train_frac),
-                                float(model.resample_padding), u_tab.data_ptr(), _lib.ptr(jitter),
-                                0 if jitter is None else jitter.shape[1], max_jitter, N, S, sdist.data_ptr(), stream))
+    s_near = s_near_of(model, train_frac)
+    tail = (u_tab.data_ptr(), _lib.ptr(jitter), 0 if jitter is None else jitter.shape[1], max_jitter, N, S, sdist.data_ptr(), stream)
+    head = (_lib.ptr(sdist_prev), _lib.ptr(wp), n_prev, dilation, anneal_of(model.anneal_slope, train_frac), float(model.resample_padding))
+    if s_near == 0:
+        _lib.check(lib.ucn_resample(*head, *tail))
+    else:                                                      # near_anneal_rate: the domain [s_near, 1] (models.py:143-146,173,200)
+        _lib.check(lib.ucn_resample_domain(*head, s_near, *tail))
     if pinned_sdist is not None:
         sdist = _f32(pinned_sdist, N, S + 1).clone()
     _lib.check(lib.ucn_cone_basis(rays.cam.data_ptr(), rvec.data_ptr(), N, basis.data_ptr(), stream))

@@ -186,6 +186,60 @@ class _Composite(torch.autograd.Function):
         return g_density, g_rgbs, None, None, None, None
 
 
+class _CompositeRays(torch.autograd.Function):
+    """`_Composite` with the per-ray colour gain [N, 3] (models.py:258-269, differentiable: its gradient reaches the exposure
+    embedding) and / or per-ray background colours [N, 3] (models.py:253-256, no gradient), each None or a tensor:
+    `ucn_composite_rays` and `ucn_composite_rays_backward`.  Fifth output: the colours as composited, gain * rgbs (what the reference's
+    in-place scaling leaves in ray_results['rgb']); None with no gain."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, density, rgbs, gain, posts, dirs, ray_bg, bg, opaque):
+        lib = _lib.load()
+        N, S = density.shape
+        density, rgbs = density.contiguous(), rgbs.contiguous()
+        gain = None if gain is None else gain.contiguous()
+        ray_bg = None if ray_bg is None else ray_bg.contiguous()
+        weights = torch.empty(N, S, device=density.device)
+        main = torch.empty(N, 5, device=density.device)
+        scaled = torch.empty_like(rgbs) if gain is not None else None         # the backward reads the unscaled colours: a second buffer
+        ctx.consts = (float(bg), int(bool(opaque)))
+        _lib.check(posts.entry(lib, 'ucn_composite_rays')(
+            density.data_ptr(), rgbs.data_ptr(), *posts.compositing(), dirs.data_ptr(), _lib.ptr(gain), _lib.ptr(ray_bg), *ctx.consts,
+            N, S, weights.data_ptr(), main.data_ptr(), None, _lib.ptr(scaled), _lib.stream()))
+        ctx.save_for_backward(density, rgbs, dirs, gain, ray_bg)
+        ctx.posts = posts
+        ctx.set_materialize_grads(False)
+        return weights, main[:, :3].contiguous(), main[:, 3].contiguous(), main[:, 4].contiguous(), scaled
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, g_w, g_rgb, g_depth, g_acc, g_scaled):
+        lib = _lib.load()
+        density, rgbs, dirs, gain, ray_bg = ctx.saved_tensors
+        N, S = density.shape
+        if g_w is None and g_rgb is None and g_depth is None and g_acc is None and g_scaled is None:
+            return (None,) * 8
+        g_main = torch.zeros(N, 5, device=density.device)
+        if g_rgb is not None:
+            g_main[:, :3] = g_rgb
+        if g_depth is not None:
+            g_main[:, 3] = g_depth
+        if g_acc is not None:
+            g_main[:, 4] = g_acc
+        g_w = None if g_w is None else g_w.float().contiguous()
+        g_scaled = None if g_scaled is None else g_scaled.float().contiguous()
+        g_density = torch.empty_like(density)
+        g_rgbs = torch.empty_like(rgbs)
+        g_gain = torch.empty(N, 3, device=density.device) if (gain is not None and ctx.needs_input_grad[2]) else None
+        posts = ctx.posts
+        _lib.check(posts.entry(lib, 'ucn_composite_rays_backward')(
+            density.data_ptr(), rgbs.data_ptr(), *posts.compositing(backward=True), dirs.data_ptr(), _lib.ptr(gain), _lib.ptr(ray_bg),
+            *ctx.consts, N, S, _lib.ptr(g_w), g_main.data_ptr(), _lib.ptr(g_scaled), g_density.data_ptr(), g_rgbs.data_ptr(),
+            _lib.ptr(g_gain), _lib.stream()))
+        return g_density, g_rgbs, g_gain, None, None, None, None, None
+
+
 class _HashDecay(torch.autograd.Function):
     """models.py:297-306 as one pass over the table forward and one backward (`ucn_hash_decay`); the per-level slices of
     the reference's formulation cost 16 full-table zero-fills and adds in autograd, the torch form of the weighted sum

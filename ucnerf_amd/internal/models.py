@@ -559,12 +559,9 @@ class Model(nn.Module):
         set_kwargs(self, kwargs)
         self.config = config
         self._raydist_curve = raydist_curve(self.raydist_fn)         # resolved once (coord.py:151-172); 0 = identity
-        for k, want in dict(learned_exposure_scaling=False, near_anneal_rate=None, single_mlp=False, distinct_prop=True,
-                            use_viewdirs=True).items():
+        for k, want in dict(single_mlp=False, distinct_prop=True, use_viewdirs=True).items():
             if getattr(self, k) != want:
                 raise NotImplementedError(f"Model.{k}={getattr(self, k)!r} is outside the shipped waymo.gin path")
-        if self.bg_intensity_range[0] != self.bg_intensity_range[1]:
-            raise NotImplementedError("random background colours (bg_intensity_range) are not on the shipped path")
         for k in ('orientation_loss_mult', 'predicted_normal_loss_mult'):
             # the only consumers of the normals' own gradient (the reference's create_graph=True, models.py:559): not built,
             # the normals are returned detached; both default to 0 (configs.py:81,85)
@@ -577,6 +574,11 @@ class Model(nn.Module):
         if self.num_glo_features > 0 and not getattr(config, 'zero_glo', False):
             # ref models.py:73-75: one appearance code per training image, looked up by batch['cam_idx']
             self.glo_vecs = nn.Embedding(self.num_glo_embeddings, self.num_glo_features)
+        if self.learned_exposure_scaling:
+            # ref models.py:77-82 (registered here, before skynerf: the state dict's key order): a learned per-exposure colour
+            # scaling, an offset from 1 that starts at 0; row 0 stays unused (march_level.ray_gain masks exposure_idx == 0)
+            self.exposure_scaling_offsets = nn.Embedding(self.num_glo_embeddings, 3)
+            torch.nn.init.zeros_(self.exposure_scaling_offsets.weight)
         if getattr(self.config, 'model_sky', False):
             self.skynerf = NeRF(D=8, d_in_view=3, W=256, multires_view=4, output_ch=4, skips=[4])
         if getattr(self.config, 'brightness_correction', False):
@@ -588,7 +590,7 @@ class Model(nn.Module):
         """ref models.py:97-365.  `batch` may carry two optional extra keys that pin the random
         draws (the reference draws them from torch's global RNG, render.py:123-124,140 and
         stepfun.py:216): 'rand_vec' [..., num_levels*3] and 'march_noise' (list of per-level dicts
-        with 'jitter', 'flip', 'spin').
+        with 'jitter', 'flip', 'spin', and 'bg' [..., 3] for the random background colours of a two-valued bg_intensity_range).
 
         Route (`Model.march_route`): 'auto' builds the differentiable graph of train_graph.py (HIP featurisation
         forward / backward, MFMA train kernels, autograd glue) only for a model in TRAINING mode with autograd enabled
@@ -737,10 +739,11 @@ class Model(nn.Module):
 
         renderings, ray_history = [], []
         posts = weights = None
+        gain = ml.ray_gain(self, batch, rays)                   # the RawNeRF exposure (None without batch['exposure_idx'])
         nerf_chunk = max(1, int(self.max_chunk_rays))
         planes = lambda m: m.encoder.num_levels + m.scale_planes()          # feature planes of level_dim floats per sample
         nerf_row = self.num_nerf_samples * planes(self.nerf_mlp) * self.nerf_mlp.encoder.level_dim
-        for i_level, is_prop, S, mlp, dilation in ml.level_plan(self):
+        for i_level, is_prop, S, mlp, dilation in ml.level_plan(self, train_frac):
             desc = mlp.field(glo_fold=not is_prop)
             L, C = mlp.encoder.num_levels, mlp.encoder.level_dim
             # max_chunk_rays is quoted for the NeRF level; a proposal level (fewer samples, narrower features) takes
@@ -831,10 +834,9 @@ class Model(nn.Module):
                     prof.append((i_level, n, e0, e1, m0, e2))      # features: e0..e1 on its stream, MLP: m0..e2
             if overlap:
                 cur.wait_stream(side)
-            _lib.check(posts.entry(lib, 'ucn_composite')(
-                density.data_ptr(), _lib.ptr(rgbs), *posts.compositing(), rays.d.data_ptr(),
-                float(self.bg_intensity_range[0]), int(bool(self.opaque_background)), N, S, weights.data_ptr(),
-                main.data_ptr(), _lib.ptr(extras), st))
+            # the level's background colours (drawn behind its MLP, models.py:256), then one launch: `rgbs` leaves it scaled by the gain
+            bg, ray_bg = ml.background(self, rays, i_level, rand)
+            ml.composite(posts, density, rgbs, rays.d, gain, ray_bg, bg, self.opaque_background, weights, main, extras, st)
             renderings.append(ml.rendering_entry(main[:, 0:3], main[:, 3], main[:, 4], weights, extras, prefix, posts.sdist, rgbs,
                                                  getattr(cfg, 'vis_num_rays', 16), normals=normals))
             if want_history:

@@ -32,7 +32,7 @@ from .head_pack import (_acc_vec, _head_gather_index, _pack_fragments, _weave, p
 from .heads_bf16 import _FusedHeads, _PropHeads, wgrad  # noqa: F401
 from .heads_f32 import (_ColourMLP, _ColourMLPComposed, _ColourMLPGlo, _FieldMLPComposed, _TallLinear,  # noqa: F401
                         tall_linear, tall_matmul)
-from .march_nodes import (GradientScaler, _AffineBlend, _Composite, _FieldFeatures, _GradChannel, _tail_fusable,  # noqa: F401
+from .march_nodes import (GradientScaler, _AffineBlend, _Composite, _CompositeRays, _FieldFeatures, _GradChannel, _tail_fusable,  # noqa: F401
                           brightness_forward, hash_decay, scale_features)
 from .sky_train import _sky_fusable, sky_forward, sky_forward_fused
 
@@ -189,7 +189,8 @@ def march_train(model, rand, batch, train_frac, compute_extras, eval_camidx, glo
     N, dev, prefix = rays.N, rays.dev, rays.prefix
     o, d, vd, cam, far = rays.o, rays.d, rays.vd, rays.cam, rays.far
     st, cfg = _lib.stream(), model.config
-    bg, opaque = float(model.bg_intensity_range[0]), int(bool(model.opaque_background))
+    opaque = int(bool(model.opaque_background))
+    gain = ml.ray_gain(model, batch, rays)                      # the RawNeRF exposure [N, 3] (None without batch['exposure_idx']); differentiable
     renderings, ray_history = [], []
     posts = weights = None
     # The sky NeRF depends on the rays only, not on the field: with `Model.sky_side_stream` its fused forward is issued FIRST, on
@@ -205,7 +206,7 @@ def march_train(model, rand, batch, train_frac, compute_extras, eval_camidx, glo
             _sky_pending = sky_forward_fused(model.skynerf, o, d, cam, far)
         for t in (o, d, cam, far):
             t.record_stream(model._sky_stream)
-    for i_level, is_prop, S, mlp, dilation in ml.level_plan(model):
+    for i_level, is_prop, S, mlp, dilation in ml.level_plan(model, train_frac):
         # 'sdist' among the pinned draws (tests/test_train_full_size.py): tells 1-ulp sample positions amplified by 2^19-wide levels from a wrong backward
         posts, flip, spin = ml.fenceposts(model, rays, i_level, S, dilation, train_frac, rand, posts, weights, st,
                                           pinned_sdist=rays.noise[i_level].get('sdist') if rand else None)
@@ -221,7 +222,15 @@ def march_train(model, rand, batch, train_frac, compute_extras, eval_camidx, glo
         density, rgbs = field_heads(mlp, feat, vd, N, S, chan, glo)
         if getattr(cfg, 'brightness_correction', False):              # models.py:233-235 (gated on this flag)
             rgbs, density = GradientScaler.apply(rgbs, density, tmean)
-        weights, c_rgb, c_depth, c_acc = _Composite.apply(density, rgbs, posts, d, bg, opaque)
+        bg, ray_bg = ml.background(model, rays, i_level, rand)        # drawn behind the level's MLP (models.py:256)
+        level_gain = None if is_prop else gain                        # a proposal level's colours are zeros (models.py:584-585): gain * 0 = 0
+        if level_gain is None and ray_bg is None:
+            weights, c_rgb, c_depth, c_acc = _Composite.apply(density, rgbs, posts, d, bg, opaque)
+        else:
+            # models.py:258-269 scales ray_results['rgb'] in place: the scaled colours are what the history and the ray bundles carry
+            weights, c_rgb, c_depth, c_acc, scaled = _CompositeRays.apply(density, rgbs, level_gain, posts, d, ray_bg, bg, opaque)
+            if level_gain is not None:
+                rgbs = scaled
         extras = None
         if compute_extras:
             # render.py:218-242: depth percentiles and the mean distance -- not differentiated by any loss of the path
@@ -229,8 +238,8 @@ def march_train(model, rand, batch, train_frac, compute_extras, eval_camidx, glo
             with torch.no_grad():
                 dn, rg = density.detach().float().contiguous(), rgbs.detach().float().contiguous()
                 w_x, main_x, extras = torch.empty(N, S, device=dev), torch.empty(N, 5, device=dev), torch.empty(N, 4, device=dev)
-                _lib.check(posts.entry(lib, 'ucn_composite')(dn.data_ptr(), rg.data_ptr(), *posts.compositing(), d.data_ptr(), bg,
-                                                             opaque, N, S, w_x.data_ptr(), main_x.data_ptr(), extras.data_ptr(), st))
+                # (`rg` are the colours as composited -- already scaled by the gain, hence none here; a detached copy, so nothing is overwritten)
+                ml.composite(posts, dn, rg, d, None, ray_bg, bg, opaque, w_x, main_x, extras, st)
         raw_grad = normals = None
         if not mlp.disable_density_normals:
             # models.py:550-567, detached (the second-order path of create_graph=True is not built: Model.__init__ refuses its
