@@ -576,6 +576,28 @@ int ucn_generate_rays(const int32_t *pix_x, const int32_t *pix_y, const int32_t 
                       uint32_t height, uint32_t n_rays, float near_, float far_, float *origins, float *directions,
                       float *viewdirs, float *radii, float *imageplane, float *cam_dirs, float *near_out,
                       float *far_out, float *lossmult_out, float *cam_idx_out, ucn_stream_t stream);
+/* ABI 32: the same with a camera model.  camera_model 0 = perspective (exactly ucn_generate_rays), 1 = the reference's
+ * `camtype == 'panoroma'` (camera_utils.py:507-510, set for the nuScenes render path at datasets.py:872-878): each of the
+ * three camera-space directions (pixel centre, +1 in x, +1 in y) goes (c0, c1, c2) -> (sin c0, c1, cos c0) after the inverse
+ * intrinsics and before the OpenCV -> OpenGL flip, in float64 with the device's double sin / cos; the rest is the
+ * perspective code.  The float32 batch is the reference's to within one float32 unit of the ray's vector norm (the device's
+ * double sin / cos are not libm's to the last bit); the perspective batch stays bit-identical.  Any other camera_model fails. */
+int ucn_generate_rays_model(const int32_t *pix_x, const int32_t *pix_y, const int32_t *cam_idx, int32_t cam_idx_scalar,
+                            const double *pixtocams, const double *camtoworlds, uint32_t n_cams, uint32_t width,
+                            uint32_t height, uint32_t n_rays, float near_, float far_, float *origins, float *directions,
+                            float *viewdirs, float *radii, float *imageplane, float *cam_dirs, float *near_out,
+                            float *far_out, float *lossmult_out, float *cam_idx_out, int camera_model, ucn_stream_t stream);
+/* ABI 32: a spherical (equirectangular) frame, ref camera_utils.py:635-678 cast_spherical_rays (`render_camtype == 'pano'`,
+ * datasets.py:574-578).  Ray (i, j) of a height x width frame, row-major: theta_j = j * (2 pi / width), phi_i = i * (pi / height)
+ * with the last grid line exactly 2 pi / pi (np.linspace), direction = R (-sin phi sin theta, cos phi, sin phi cos theta), R =
+ * camtoworld[:3, :3]; radii from the differences to the (i, j + 1) and (i + 1, j) directions, which each thread computes itself
+ * (no (height + 1) x (width + 1) grid in memory).  Float64 arithmetic, one rounding at the float32 store.
+ * camtoworld DEVICE double [3,4].  Outputs float32: origins / directions / viewdirs (= directions, NOT renormalised, as in the
+ * reference) / cam_dirs (= -R[:, 2], datasets.py:446) [n,3], radii [n,1], imageplane [n,2]|NULL (zeros), and the columns
+ * near / far / lossmult (1) / cam_idx (0) [n,1] (each may be NULL); n = width * height, 0 returns 0 without a launch. */
+int ucn_spherical_rays(const double *camtoworld, uint32_t width, uint32_t height, float near_, float far_, float *origins,
+                       float *directions, float *viewdirs, float *radii, float *imageplane, float *cam_dirs, float *near_out,
+                       float *far_out, float *lossmult_out, float *cam_idx_out, ucn_stream_t stream);
 
 /* ------------------------------------------------- sky layer + colour correction
  * ref: models.py:326-337,743-904 (sky NeRF, 120 samples, 8x256 MLP) and

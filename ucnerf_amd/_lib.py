@@ -11,7 +11,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # UCN_LIB_PATH: another build of the same ABI for A/B measurements; default = the in-tree product
 LIB_PATH = os.environ.get("UCN_LIB_PATH") or os.path.join(_HERE, "csrc", "libucnerf_march.so")
-ABI_VERSION = 31
+ABI_VERSION = 32
 LAUNCH_CORESIDENT = 0x100  # include/ucnerf_march.h UCN_LAUNCH_CORESIDENT
 TABLE_F16 = 0x200
 RAYS_INCOHERENT = 0x1000   # ucn_march_features layout flag: random (training) rays -> lane-paired fetch on every hashed level
@@ -120,6 +120,9 @@ SIGNATURES = {
                                           c_vp],
     "ucn_generate_rays": [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_u32, c_u32, c_u32, c_u32, c_f32, c_f32, c_vp, c_vp, c_vp,
                           c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "ucn_generate_rays_model": [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_u32, c_u32, c_u32, c_u32, c_f32, c_f32, c_vp, c_vp, c_vp,
+                                c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp],
+    "ucn_spherical_rays": [c_vp, c_u32, c_u32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "ucn_adam_step": [c_vp, c_vp, c_vp, c_vp, c_u64, c_f32, c_f32, c_f32, c_f32, c_u32, c_i32, c_vp],
     "ucn_distortion_loss": [c_vp, c_vp, c_u32, c_u32, c_vp, c_vp, c_vp],
     "ucn_img_warping": [c_vp, c_vp, c_vp, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp],
