@@ -325,6 +325,39 @@ int ucn_march_density_grad(const ucn_field_t *f, const float *fenceposts, const 
 int ucn_points_density_grad(const ucn_field_t *f, const float *means, const float *stds, uint32_t B, uint32_t G, int warp,
                             const float *gfeat, float *raw_grad_out, float *normals_out, ucn_stream_t stream);
 
+/* ------------------------------------------------- the ray path with the field's warp as an argument (added within ABI 32;
+ * ref: MLP.warp_fn, models.py:392 and :488-494; coord.py:93-96 track_linearize knows 'contract' and None)
+ * warp = 1: 'contract' -- each call below is then the entry point of the same name without `_warp` (or its `_tdist` sibling), which
+ * are calls of these.  warp = 0: warp_fn = None, a bounded scene inside [-1, 1]^3 -- the cast Gaussians reach the grid as they are:
+ * u = (mean + 1) / 2, the damping argument from the uncontracted, unhalved std, coord_out the plain mean of the six means.  A
+ * multisample outside [0, 1]^3 (bounds inclusive) adds no grid feature, still counts in the mean of six, receives no table
+ * gradient, and keeps its erf weight in the scale features.  Any other warp is refused.
+ * fenceposts: sdist [N,S+1] read with near_ / far_, or -- near_ = far_ = NULL -- metric tdist (ucn_s_to_t), the convention of
+ * ucn_march_density_grad.  Every other argument as in the call without `_warp`.
+ * ucn_cast_probe_warp with warp = 0: floats 5..8 of a point repeat its cast mean and std, float 9 is 1 / sqrt(8 std^2). */
+int ucn_march_features_warp(const ucn_field_t *f, const float *fenceposts, const float *near_, const float *far_,
+                            const float *origins, const float *directions, const float *basis, const float *radii,
+                            const float *flip, const float *spin, float std_scale, int warp, uint32_t N, uint32_t S,
+                            uint32_t levels_per_block, int sample_major, float *features_out, float *coord_out,
+                            float *tmean_out, ucn_stream_t stream);
+int ucn_march_features_backward_warp(const ucn_field_t *f, const float *fenceposts, const float *near_, const float *far_,
+                                     const float *origins, const float *directions, const float *basis, const float *radii,
+                                     const float *flip, const float *spin, float std_scale, int warp, uint32_t N, uint32_t S,
+                                     uint32_t levels_per_block, int sample_major, const float *grad_features,
+                                     float *grad_embeddings, float *workspace, ucn_stream_t stream);
+int ucn_march_scale_features_warp(const ucn_field_t *f, const float *fenceposts, const float *near_, const float *far_,
+                                  const float *origins, const float *directions, const float *basis, const float *radii,
+                                  const float *flip, const float *spin, float std_scale, int warp, uint32_t N, uint32_t S,
+                                  const float *level_scale, int layout, float *scale_out, ucn_stream_t stream);
+int ucn_march_density_grad_warp(const ucn_field_t *f, const float *fenceposts, const float *near_, const float *far_,
+                                const float *origins, const float *directions, const float *basis, const float *radii,
+                                const float *flip, const float *spin, float std_scale, int warp, uint32_t N, uint32_t S,
+                                int layout, const float *gfeat, float *raw_grad_out, float *normals_out, ucn_stream_t stream);
+int ucn_cast_probe_warp(const float *fenceposts, const float *near_, const float *far_, const float *origins,
+                        const float *directions, const float *basis, const float *radii, const float *flip /*|NULL*/,
+                        const float *spin /*|NULL*/, float std_scale, int warp, uint32_t N, uint32_t S, float *out,
+                        ucn_stream_t stream);
+
 /* ref: coord.py:214-225 pos_enc(viewdirs): the per-ray direction inputs of the colour MLP.
  * mlp_mode 0: folded through the direction columns of lin_second_stage_{0,1} into additive terms
  *             [N,2,n_width];  mlp_mode 1: the encoding itself as one 32-wide input tile [N,32]

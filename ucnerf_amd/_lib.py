@@ -101,6 +101,16 @@ SIGNATURES = {
     "ucn_density_feature_grad": [ctypes.POINTER(UcnField), c_vp, c_u32, c_vp, c_vp],
     "ucn_march_density_grad": [ctypes.POINTER(UcnField), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_u32, c_u32, c_i32,
                                c_vp, c_vp, c_vp, c_vp],
+    # the ray path with the field's warp (MLP.warp_fn: 1 = 'contract', 0 = None) as an argument; near = far = NULL: metric fenceposts
+    "ucn_march_features_warp": [ctypes.POINTER(UcnField), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i32,
+                                c_u32, c_u32, c_u32, c_i32, c_vp, c_vp, c_vp, c_vp],
+    "ucn_march_features_backward_warp": [ctypes.POINTER(UcnField), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i32,
+                                         c_u32, c_u32, c_u32, c_i32, c_vp, c_vp, c_vp, c_vp],
+    "ucn_march_scale_features_warp": [ctypes.POINTER(UcnField), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i32,
+                                      c_u32, c_u32, c_vp, c_i32, c_vp, c_vp],
+    "ucn_march_density_grad_warp": [ctypes.POINTER(UcnField), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i32,
+                                    c_u32, c_u32, c_i32, c_vp, c_vp, c_vp, c_vp],
+    "ucn_cast_probe_warp": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i32, c_u32, c_u32, c_vp, c_vp],
     "ucn_points_density_grad": [ctypes.POINTER(UcnField), c_vp, c_vp, c_u32, c_u32, c_i32, c_vp, c_vp, c_vp, c_vp],
     "ucn_field_dir_floats": [ctypes.POINTER(UcnField), c_u32],
     "ucn_field_dir_bias": [ctypes.POINTER(UcnField), c_vp, c_u32, c_vp, c_vp],

@@ -88,7 +88,10 @@ UCN_SAME_IN_EVERY_UNIT __device__ __forceinline__ void contract_to_unit(float x,
 // The six multisample Gaussians of sample (ray, s): render.py:108-152 then contract_to_unit.
 // Shared by the forward and the backward kernel (the backward recomputes it instead of reading back
 // 6x4 floats per sample).  TD: in.sdist holds metric fenceposts (see RayInputs).
-template <bool TD = false>
+// WARP = false (MLP.warp_fn = None, a bounded scene): the Gaussians reach the grid as cast, u = (x + 1) / 2 and std unscaled.
+// A template argument, not a run-time one: with WARP = true the body is the one every kernel inlined before the argument
+// existed, so those kernels keep their machine code (profiles/unwarped/isa_identity.txt).
+template <bool TD = false, bool WARP = true>
 UCN_SAME_IN_EVERY_UNIT __device__ __forceinline__ void cast_sample(const RayInputs &in, const HexPattern &hx, float std_scale, uint32_t ray,
                                             uint32_t s, uint32_t S, float (&u)[6][3], float (&rs)[6],
                                             float (&csum)[3], float &tsum, float *probe = nullptr) {
@@ -147,11 +150,11 @@ UCN_SAME_IN_EVERY_UNIT __device__ __forceinline__ void cast_sample(const RayInpu
             // ucn_cast_probe: what render.cast_rays returns (means, stds, t) and what the grid sees behind the contraction
             float *pr = probe + j * UCN_CAST_PROBE_FLOATS;
             float sdc;
-            contract_to_unit(wx, wy, wz, sd_unit * t, true, u[j][0], u[j][1], u[j][2], rs[j], c0, c1, c2, &sdc);
+            contract_to_unit(wx, wy, wz, sd_unit * t, WARP, u[j][0], u[j][1], u[j][2], rs[j], c0, c1, c2, &sdc);
             pr[0] = wx; pr[1] = wy; pr[2] = wz; pr[3] = sd_unit * t; pr[4] = t;
             pr[5] = c0; pr[6] = c1; pr[7] = c2; pr[8] = sdc; pr[9] = rs[j];
         } else {
-            contract_to_unit(wx, wy, wz, sd_unit * t, true, u[j][0], u[j][1], u[j][2], rs[j], c0, c1, c2);
+            contract_to_unit(wx, wy, wz, sd_unit * t, WARP, u[j][0], u[j][1], u[j][2], rs[j], c0, c1, c2);
         }
         csum[0] += c0; csum[1] += c1; csum[2] += c2; tsum += t;
     }

@@ -350,15 +350,26 @@ __device__ __forceinline__ void featurise(const UcnLevels &lvls, const TT *__res
 
 // Introspection for the parity tests: the product's own cast_sample / contract_to_unit, results
 // written out instead of consumed.
-template <bool TD = false>
-__global__ __launch_bounds__(256) void k_cast_probe(RayInputs in, HexPattern hx, float std_scale, uint32_t N, uint32_t S,
-                                                    float *__restrict__ out) {
+template <bool TD, bool WARP>
+__device__ __forceinline__ void cast_probe_body(const RayInputs &in, const HexPattern &hx, float std_scale, uint32_t N, uint32_t S,
+                                                float *__restrict__ out) {
     const size_t B = (size_t)N * S;
     const size_t b = (size_t)blockIdx.x * 256u + threadIdx.x;
     if (b >= B) return;
     const uint32_t ray = (uint32_t)(b / S), s = (uint32_t)(b - (size_t)ray * S);
     float u[6][3], rs[6], csum[3], tsum;
-    cast_sample<TD>(in, hx, std_scale, ray, s, S, u, rs, csum, tsum, out + b * 6 * UCN_CAST_PROBE_FLOATS);
+    cast_sample<TD, WARP>(in, hx, std_scale, ray, s, S, u, rs, csum, tsum, out + b * 6 * UCN_CAST_PROBE_FLOATS);
+}
+template <bool TD = false>
+__global__ __launch_bounds__(256) void k_cast_probe(RayInputs in, HexPattern hx, float std_scale, uint32_t N, uint32_t S,
+                                                    float *__restrict__ out) {
+    cast_probe_body<TD, true>(in, hx, std_scale, N, S, out);
+}
+// MLP.warp_fn = None: floats 5..8 of a point repeat its cast mean and std, 9 is 1 / sqrt(8 std^2) of the uncontracted std
+template <bool TD = false>
+__global__ __launch_bounds__(256) void k_cast_probe_unwarped(RayInputs in, HexPattern hx, float std_scale, uint32_t N, uint32_t S,
+                                                             float *__restrict__ out) {
+    cast_probe_body<TD, false>(in, hx, std_scale, N, S, out);
 }
 
 __global__ __launch_bounds__(256) void k_contract_probe(const float *__restrict__ means, const float *__restrict__ stds,
@@ -437,7 +448,7 @@ static LevelGroups make_groups(const UcnLevels &lv, uint32_t levels_per_block, b
 // FEW_LEVELS is a NAME TAG only (same code): grids of <= 8 levels (the proposal fields: L = 6) and of more (the NeRF field:
 // L = 16 / 10) get distinct kernel names, so that a rocprofv3 --stats summary separates the proposal-level from the
 // NeRF-level launches without subtracting one from the other.
-template <uint32_t C, uint32_t TPB, typename TT, bool TD>
+template <uint32_t C, uint32_t TPB, typename TT, bool TD, bool WARP = true>
 __device__ __forceinline__ void march_features_body(const UcnLevels &lvls, const TT *__restrict__ table, const RayInputs &in,
                                                     const HexPattern &hx, float std_scale, uint32_t N, uint32_t S,
                                                     const LevelGroups &grp, int layout,
@@ -458,7 +469,7 @@ __device__ __forceinline__ void march_features_body(const UcnLevels &lvls, const
     if ((layout & 3) == 2) { s = (uint32_t)(b / N); ray = (uint32_t)(b - (size_t)s * N); }
     else { ray = (uint32_t)(b / S); s = (uint32_t)(b - (size_t)ray * S); }
     float u[6][3], rs[6], csum[3], tsum;
-    cast_sample<TD>(in, hx, std_scale, ray, s, S, u, rs, csum, tsum);
+    cast_sample<TD, WARP>(in, hx, std_scale, ray, s, S, u, rs, csum, tsum);
     const uint32_t i0 = grp.lo[blockIdx.y], i1 = grp.lo[blockIdx.y + 1];
     const auto level_of = [&grp](uint32_t i) -> uint32_t { return grp.list[i]; };
     const bool full_wave = __ballot(true) == ~0ull;                  // the lane-paired fetch trades rows between lanes i and i + 32
@@ -490,6 +501,17 @@ __global__ __launch_bounds__(TPB) void k_march_features_td(UcnLevels lvls, const
                                                            LevelGroups grp, int layout, float *__restrict__ features,
                                                            float *__restrict__ coord_out, float *__restrict__ tmean_out) {
     march_features_body<C, TPB, TT, true>(lvls, table, in, hx, std_scale, N, S, grp, layout, features, coord_out, tmean_out);
+}
+
+// MLP.warp_fn = None (a bounded scene inside [-1, 1]^3): the Gaussians go to the grid as cast, points outside the cube add
+// nothing (in_unit_cube, bounds inclusive) and still count in the mean of six.  Kernels of their own name with the fencepost
+// kind as a template argument, FEW_LEVELS last as above; the warped kernels keep their symbols and their code.
+template <uint32_t C, uint32_t TPB, typename TT = float, bool TD = false, bool FEW_LEVELS = false>
+__global__ __launch_bounds__(TPB) void k_march_features_unwarped(UcnLevels lvls, const TT *__restrict__ table, RayInputs in,
+                                                                 HexPattern hx, float std_scale, uint32_t N, uint32_t S,
+                                                                 LevelGroups grp, int layout, float *__restrict__ features,
+                                                                 float *__restrict__ coord_out, float *__restrict__ tmean_out) {
+    march_features_body<C, TPB, TT, TD, false>(lvls, table, in, hx, std_scale, N, S, grp, layout, features, coord_out, tmean_out);
 }
 
 // predict_density's featurisation for caller-supplied Gaussians (extract.py / API parity)
@@ -526,7 +548,7 @@ __global__ __launch_bounds__(256) void k_points_features(UcnLevels lvls, const f
 template <bool TD>
 static int march_features_launch(const ucn_field_t *f, const RayInputs &in, float std_scale, uint32_t N, uint32_t S,
                                  uint32_t levels_per_block, int layout, float *features_out, float *coord_out, float *tmean_out,
-                                 ucn_stream_t stream) {
+                                 ucn_stream_t stream, bool warp = true) {
     UCN_REQUIRE(N == 0 || (in.sdist && (TD || (in.near_ && in.far_)) && in.origins && in.dirs && in.basis && in.radii && features_out),
                 "march_features: null pointer argument");
     UCN_REQUIRE((in.flip == nullptr) == (in.spin == nullptr), "march_features: flip and spin come together");
@@ -568,9 +590,23 @@ static int march_features_launch(const ucn_field_t *f, const RayInputs &in, floa
             hipLaunchKernelGGL((KF<CC, 256, float, FEW>), grid, dim3(256), lds, st, lv, f->embeddings, in, hx, std_scale, N, S, \
                                grp, layout, features_out, coord_out, tmean_out);                                          \
     } while (0)
+#define UCN_MF3U(CC, FEW)                                                                                                 \
+    do {                                                                                                                  \
+        if (half_table)                                                                                                   \
+            hipLaunchKernelGGL((k_march_features_unwarped<CC, 256, _Float16, TD, FEW>), grid, dim3(256), lds, st, lv,         \
+                               reinterpret_cast<const _Float16 *>(f->embeddings), in, hx, std_scale, N, S, grp, layout,   \
+                               features_out, coord_out, tmean_out);                                                       \
+        else if (coresident)                                                                                              \
+            hipLaunchKernelGGL((k_march_features_unwarped<CC, 512, float, TD, FEW>), grid, dim3(512), lds, st, lv, f->embeddings, in, \
+                               hx, std_scale, N, S, grp, layout, features_out, coord_out, tmean_out);                       \
+        else                                                                                                              \
+            hipLaunchKernelGGL((k_march_features_unwarped<CC, 256, float, TD, FEW>), grid, dim3(256), lds, st, lv, f->embeddings, in, \
+                               hx, std_scale, N, S, grp, layout, features_out, coord_out, tmean_out);                       \
+    } while (0)
 #define UCN_MF2(CC, FEW)                                                                                                  \
     do {                                                                                                                  \
-        if constexpr (TD) UCN_MF3(k_march_features_td, CC, FEW);                                                          \
+        if (!warp) UCN_MF3U(CC, FEW);                                                                                     \
+        else if constexpr (TD) UCN_MF3(k_march_features_td, CC, FEW);                                                     \
         else UCN_MF3(k_march_features, CC, FEW);                                                                          \
     } while (0)
     ucn_for_level_dim(lv.C, [&](auto cc) {
@@ -579,9 +615,25 @@ static int march_features_launch(const ucn_field_t *f, const RayInputs &in, floa
         else UCN_MF2(CC, false);
     });
 #undef UCN_MF3
+#undef UCN_MF3U
 #undef UCN_MF2
     UCN_LAUNCH_CHECK("march_features");
     return 0;
+}
+
+extern "C" int ucn_march_features_warp(const ucn_field_t *f, const float *fenceposts, const float *near_, const float *far_,
+                                       const float *origins, const float *directions, const float *basis, const float *radii,
+                                       const float *flip, const float *spin, float std_scale, int warp, uint32_t N, uint32_t S,
+                                       uint32_t levels_per_block, int layout, float *features_out, float *coord_out,
+                                       float *tmean_out, ucn_stream_t stream) {
+    UCN_REQUIRE(warp == 0 || warp == 1, "march_features: warp must be 0 (MLP.warp_fn = None) or 1 ('contract'), got %d", warp);
+    UCN_REQUIRE(N == 0 || (near_ == nullptr) == (far_ == nullptr), "march_features: near and far come together (both NULL: metric fenceposts)");
+    const RayInputs in{fenceposts, near_, far_, origins, directions, basis, radii, flip, spin};
+    if (near_ == nullptr)
+        return march_features_launch<true>(f, in, std_scale, N, S, levels_per_block, layout, features_out, coord_out, tmean_out,
+                                           stream, warp != 0);
+    return march_features_launch<false>(f, in, std_scale, N, S, levels_per_block, layout, features_out, coord_out, tmean_out,
+                                        stream, warp != 0);
 }
 
 extern "C" int ucn_march_features(const ucn_field_t *f, const float *sdist, const float *near_, const float *far_,
@@ -589,9 +641,9 @@ extern "C" int ucn_march_features(const ucn_field_t *f, const float *sdist, cons
                                   const float *radii, const float *flip, const float *spin, float std_scale,
                                   uint32_t N, uint32_t S, uint32_t levels_per_block, int layout,
                                   float *features_out, float *coord_out, float *tmean_out, ucn_stream_t stream) {
-    const RayInputs in{sdist, near_, far_, origins, directions, basis, radii, flip, spin};
-    return march_features_launch<false>(f, in, std_scale, N, S, levels_per_block, layout, features_out, coord_out, tmean_out,
-                                        stream);
+    UCN_REQUIRE(N == 0 || (near_ && far_), "march_features: null pointer argument");
+    return ucn_march_features_warp(f, sdist, near_, far_, origins, directions, basis, radii, flip, spin, std_scale, 1, N, S,
+                                   levels_per_block, layout, features_out, coord_out, tmean_out, stream);
 }
 
 extern "C" int ucn_march_features_tdist(const ucn_field_t *f, const float *tdist, const float *origins,
@@ -599,35 +651,50 @@ extern "C" int ucn_march_features_tdist(const ucn_field_t *f, const float *tdist
                                         const float *spin, float std_scale, uint32_t N, uint32_t S, uint32_t levels_per_block,
                                         int layout, float *features_out, float *coord_out, float *tmean_out,
                                         ucn_stream_t stream) {
-    const RayInputs in{tdist, nullptr, nullptr, origins, directions, basis, radii, flip, spin};
-    return march_features_launch<true>(f, in, std_scale, N, S, levels_per_block, layout, features_out, coord_out, tmean_out,
-                                       stream);
+    return ucn_march_features_warp(f, tdist, nullptr, nullptr, origins, directions, basis, radii, flip, spin, std_scale, 1, N, S,
+                                   levels_per_block, layout, features_out, coord_out, tmean_out, stream);
 }
 
 template <bool TD>
-static int cast_probe_launch(const RayInputs &in, float std_scale, uint32_t N, uint32_t S, float *out, ucn_stream_t stream) {
+static int cast_probe_launch(const RayInputs &in, float std_scale, uint32_t N, uint32_t S, float *out, ucn_stream_t stream,
+                             bool warp = true) {
     UCN_REQUIRE(N == 0 || (in.sdist && (TD || (in.near_ && in.far_)) && in.origins && in.dirs && in.basis && in.radii && out),
                 "cast_probe: null pointer argument");
     UCN_REQUIRE((in.flip == nullptr) == (in.spin == nullptr), "cast_probe: flip and spin come together");
     if (N == 0 || S == 0) return 0;
-    hipLaunchKernelGGL(k_cast_probe<TD>, dim3(ucn_div_up((size_t)N * S, 256)), dim3(256), 0, (hipStream_t)stream, in, make_hex(),
-                       std_scale, N, S, out);
+    if (warp)
+        hipLaunchKernelGGL(k_cast_probe<TD>, dim3(ucn_div_up((size_t)N * S, 256)), dim3(256), 0, (hipStream_t)stream, in, make_hex(),
+                           std_scale, N, S, out);
+    else
+        hipLaunchKernelGGL(k_cast_probe_unwarped<TD>, dim3(ucn_div_up((size_t)N * S, 256)), dim3(256), 0, (hipStream_t)stream, in,
+                           make_hex(), std_scale, N, S, out);
     UCN_LAUNCH_CHECK("cast_probe");
     return 0;
+}
+
+extern "C" int ucn_cast_probe_warp(const float *fenceposts, const float *near_, const float *far_, const float *origins,
+                                   const float *directions, const float *basis, const float *radii, const float *flip,
+                                   const float *spin, float std_scale, int warp, uint32_t N, uint32_t S, float *out,
+                                   ucn_stream_t stream) {
+    UCN_REQUIRE(warp == 0 || warp == 1, "cast_probe: warp must be 0 (MLP.warp_fn = None) or 1 ('contract'), got %d", warp);
+    UCN_REQUIRE(N == 0 || (near_ == nullptr) == (far_ == nullptr), "cast_probe: near and far come together (both NULL: metric fenceposts)");
+    const RayInputs in{fenceposts, near_, far_, origins, directions, basis, radii, flip, spin};
+    if (near_ == nullptr) return cast_probe_launch<true>(in, std_scale, N, S, out, stream, warp != 0);
+    return cast_probe_launch<false>(in, std_scale, N, S, out, stream, warp != 0);
 }
 
 extern "C" int ucn_cast_probe(const float *sdist, const float *near_, const float *far_, const float *origins,
                               const float *directions, const float *basis, const float *radii, const float *flip,
                               const float *spin, float std_scale, uint32_t N, uint32_t S, float *out, ucn_stream_t stream) {
-    return cast_probe_launch<false>(RayInputs{sdist, near_, far_, origins, directions, basis, radii, flip, spin}, std_scale, N, S,
-                                    out, stream);
+    UCN_REQUIRE(N == 0 || (near_ && far_), "cast_probe: null pointer argument");
+    return ucn_cast_probe_warp(sdist, near_, far_, origins, directions, basis, radii, flip, spin, std_scale, 1, N, S, out, stream);
 }
 
 extern "C" int ucn_cast_probe_tdist(const float *tdist, const float *origins, const float *directions, const float *basis,
                                     const float *radii, const float *flip, const float *spin, float std_scale, uint32_t N,
                                     uint32_t S, float *out, ucn_stream_t stream) {
-    return cast_probe_launch<true>(RayInputs{tdist, nullptr, nullptr, origins, directions, basis, radii, flip, spin}, std_scale, N,
-                                   S, out, stream);
+    return ucn_cast_probe_warp(tdist, nullptr, nullptr, origins, directions, basis, radii, flip, spin, std_scale, 1, N, S, out,
+                               stream);
 }
 
 extern "C" int ucn_contract_probe(const float *means, const float *stds, uint32_t B, float *out_mean, float *out_std,

@@ -53,10 +53,12 @@ __device__ __forceinline__ void scale_features_store(const ScaleLevels &sl, cons
     }
 }
 
-template <uint32_t C, bool TD>
-__global__ __launch_bounds__(256) void k_march_scale_features(ScaleLevels sl, const float *__restrict__ level_scale, RayInputs in,
-                                                              HexPattern hx, float std_scale, uint32_t N, uint32_t S, int layout,
-                                                              float *__restrict__ scale_out) {
+// WARP = false (MLP.warp_fn = None): the damping of the uncontracted std.  A point outside the unit cube adds no grid feature but
+// keeps its erf weight here -- models.py:505 averages the weights over all six -- so nothing in this unit looks at u.
+template <uint32_t C, bool TD, bool WARP>
+__device__ __forceinline__ void march_scale_features_body(const ScaleLevels &sl, const float *__restrict__ level_scale,
+                                                          const RayInputs &in, const HexPattern &hx, float std_scale, uint32_t N,
+                                                          uint32_t S, int layout, float *__restrict__ scale_out) {
     const size_t B = (size_t)N * S;
     const size_t b = (size_t)blockIdx.x * 256u + threadIdx.x;
     if (b >= B) return;
@@ -64,8 +66,20 @@ __global__ __launch_bounds__(256) void k_march_scale_features(ScaleLevels sl, co
     if (layout == 2) { s = (uint32_t)(b / N); ray = (uint32_t)(b - (size_t)s * N); }
     else { ray = (uint32_t)(b / S); s = (uint32_t)(b - (size_t)ray * S); }
     float u[6][3], rs[6], csum[3], tsum;
-    cast_sample<TD>(in, hx, std_scale, ray, s, S, u, rs, csum, tsum);
+    cast_sample<TD, WARP>(in, hx, std_scale, ray, s, S, u, rs, csum, tsum);
     scale_features_store<C>(sl, level_scale, rs, 6, B, b, scale_out, layout == 1);
+}
+template <uint32_t C, bool TD>
+__global__ __launch_bounds__(256) void k_march_scale_features(ScaleLevels sl, const float *__restrict__ level_scale, RayInputs in,
+                                                              HexPattern hx, float std_scale, uint32_t N, uint32_t S, int layout,
+                                                              float *__restrict__ scale_out) {
+    march_scale_features_body<C, TD, true>(sl, level_scale, in, hx, std_scale, N, S, layout, scale_out);
+}
+template <uint32_t C, bool TD>
+__global__ __launch_bounds__(256) void k_march_scale_features_unwarped(ScaleLevels sl, const float *__restrict__ level_scale,
+                                                                       RayInputs in, HexPattern hx, float std_scale, uint32_t N,
+                                                                       uint32_t S, int layout, float *__restrict__ scale_out) {
+    march_scale_features_body<C, TD, false>(sl, level_scale, in, hx, std_scale, N, S, layout, scale_out);
 }
 
 template <uint32_t C>
@@ -139,7 +153,8 @@ ScaleLevels scale_levels(const UcnLevels &lv) {
 
 template <bool TD>
 static int march_scale_features_launch(const ucn_field_t *f, const RayInputs &in, float std_scale, uint32_t N, uint32_t S,
-                                       const float *level_scale, int layout, float *scale_out, ucn_stream_t stream) {
+                                       const float *level_scale, int layout, float *scale_out, ucn_stream_t stream,
+                                       bool warp = true) {
     UCN_REQUIRE(N == 0 || (in.sdist && (TD || (in.near_ && in.far_)) && in.origins && in.dirs && in.basis && in.radii && level_scale &&
                            scale_out), "march_scale_features: null pointer argument");
     UCN_REQUIRE((in.flip == nullptr) == (in.spin == nullptr), "march_scale_features: flip and spin come together");
@@ -153,27 +168,45 @@ static int march_scale_features_launch(const ucn_field_t *f, const RayInputs &in
     const HexPattern hx = make_hex();
     const dim3 grid(ucn_div_up(B, 256));
     ucn_for_level_dim(lv.C, [&](auto cc) {
-        hipLaunchKernelGGL((k_march_scale_features<decltype(cc)::value, TD>), grid, dim3(256), 0, (hipStream_t)stream, sl, level_scale,
-                           in, hx, std_scale, N, S, layout, scale_out);
+        if (warp)
+            hipLaunchKernelGGL((k_march_scale_features<decltype(cc)::value, TD>), grid, dim3(256), 0, (hipStream_t)stream, sl, level_scale,
+                               in, hx, std_scale, N, S, layout, scale_out);
+        else
+            hipLaunchKernelGGL((k_march_scale_features_unwarped<decltype(cc)::value, TD>), grid, dim3(256), 0, (hipStream_t)stream, sl,
+                               level_scale, in, hx, std_scale, N, S, layout, scale_out);
     });
     UCN_LAUNCH_CHECK("march_scale_features");
     return 0;
+}
+
+extern "C" int ucn_march_scale_features_warp(const ucn_field_t *f, const float *fenceposts, const float *near_, const float *far_,
+                                             const float *origins, const float *directions, const float *basis,
+                                             const float *radii, const float *flip, const float *spin, float std_scale, int warp,
+                                             uint32_t N, uint32_t S, const float *level_scale, int layout, float *scale_out,
+                                             ucn_stream_t stream) {
+    UCN_REQUIRE(warp == 0 || warp == 1, "march_scale_features: warp must be 0 (MLP.warp_fn = None) or 1 ('contract'), got %d", warp);
+    UCN_REQUIRE(N == 0 || (near_ == nullptr) == (far_ == nullptr),
+                "march_scale_features: near and far come together (both NULL: metric fenceposts)");
+    const RayInputs in{fenceposts, near_, far_, origins, directions, basis, radii, flip, spin};
+    if (near_ == nullptr) return march_scale_features_launch<true>(f, in, std_scale, N, S, level_scale, layout, scale_out, stream, warp != 0);
+    return march_scale_features_launch<false>(f, in, std_scale, N, S, level_scale, layout, scale_out, stream, warp != 0);
 }
 
 extern "C" int ucn_march_scale_features(const ucn_field_t *f, const float *sdist, const float *near_, const float *far_,
                                         const float *origins, const float *directions, const float *basis, const float *radii,
                                         const float *flip, const float *spin, float std_scale, uint32_t N, uint32_t S,
                                         const float *level_scale, int layout, float *scale_out, ucn_stream_t stream) {
-    const RayInputs in{sdist, near_, far_, origins, directions, basis, radii, flip, spin};
-    return march_scale_features_launch<false>(f, in, std_scale, N, S, level_scale, layout, scale_out, stream);
+    UCN_REQUIRE(N == 0 || (near_ && far_), "march_scale_features: null pointer argument");
+    return ucn_march_scale_features_warp(f, sdist, near_, far_, origins, directions, basis, radii, flip, spin, std_scale, 1, N, S,
+                                         level_scale, layout, scale_out, stream);
 }
 
 extern "C" int ucn_march_scale_features_tdist(const ucn_field_t *f, const float *tdist, const float *origins,
                                               const float *directions, const float *basis, const float *radii, const float *flip,
                                               const float *spin, float std_scale, uint32_t N, uint32_t S, const float *level_scale,
                                               int layout, float *scale_out, ucn_stream_t stream) {
-    const RayInputs in{tdist, nullptr, nullptr, origins, directions, basis, radii, flip, spin};
-    return march_scale_features_launch<true>(f, in, std_scale, N, S, level_scale, layout, scale_out, stream);
+    return ucn_march_scale_features_warp(f, tdist, nullptr, nullptr, origins, directions, basis, radii, flip, spin, std_scale, 1, N, S,
+                                         level_scale, layout, scale_out, stream);
 }
 
 extern "C" int ucn_points_scale_features(const ucn_field_t *f, const float *means, const float *stds, uint32_t B, uint32_t G,

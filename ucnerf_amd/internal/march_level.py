@@ -192,9 +192,20 @@ class Fenceposts:
             None if flip is None else flip[sl].data_ptr(), None if spin is None else spin[sl].data_ptr()]
 
     def normals_geometry(self, rays, flip, spin, sl=slice(None)):
-        """`geometry` for ucn_march_density_grad, which has no `_tdist` sibling: metric fenceposts go with near = far = NULL."""
+        """`geometry` for the entry points without a `_tdist` sibling (`ray_call`): metric fenceposts go with near = far = NULL."""
         g = self.geometry(rays, flip, spin, sl)
         return g if self.tdist is None else [g[0], None, None] + g[1:]
+
+    def ray_call(self, lib, name, field, rays, flip, spin, sl, std_scale, warp, *tail):
+        """One of the ray-path entry points -- ucn_march_features[_backward], ucn_march_scale_features, ucn_march_density_grad -- for a
+        field of the given warp (MLP.warp: 1 = 'contract', 0 = warp_fn None): lib.<name>[_tdist](field, geometry, std_scale, *tail) or
+        lib.<name>_warp(field, fenceposts, near, far, cones, std_scale, 0, *tail)."""
+        if not warp:
+            return getattr(lib, name + '_warp')(field, *self.normals_geometry(rays, flip, spin, sl), float(std_scale), 0, *tail)
+        # 'contract': the entry points the warped field always called (themselves calls of the above with warp = 1)
+        if name == 'ucn_march_density_grad':
+            return lib.ucn_march_density_grad(field, *self.normals_geometry(rays, flip, spin, sl), float(std_scale), *tail)
+        return self.entry(lib, name)(field, *self.geometry(rays, flip, spin, sl), float(std_scale), *tail)
 
     def compositing(self, sl=slice(None), backward=False):
         """The compositing arguments for the rays `sl`; the forward `_tdist` sibling also reads the batch's metric far."""
@@ -234,8 +245,8 @@ def density_normals(mlp, posts, rays, flip, spin, sl, n, S, std_scale, layout, f
     lib = _lib.load()
     d = mlp.normals_field() if field is None else field
     _lib.check(lib.ucn_density_feature_grad(ctypes.byref(d), feat.data_ptr(), n * S, feat.data_ptr(), stream))
-    _lib.check(lib.ucn_march_density_grad(ctypes.byref(d), *posts.normals_geometry(rays, flip, spin, sl), float(std_scale), n, S, layout,
-                                          feat.data_ptr(), raw_grad[sl].data_ptr(), normals[sl].data_ptr(), stream))
+    _lib.check(posts.ray_call(lib, 'ucn_march_density_grad', ctypes.byref(d), rays, flip, spin, sl, std_scale, mlp.warp, n, S, layout,
+                              feat.data_ptr(), raw_grad[sl].data_ptr(), normals[sl].data_ptr(), stream))
 
 
 # ---- result dictionaries (the keys of ref models.py:262-324) -------------------------------------------------------------

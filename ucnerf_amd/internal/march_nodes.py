@@ -40,8 +40,8 @@ class _FieldFeatures(torch.autograd.Function):
         feat = torch.empty(N * S, L * C, device=embeddings.device)
         coord = torch.empty(N, S, 3, device=embeddings.device)
         tmean = torch.empty(N, S, device=embeddings.device)
-        _lib.check(posts.entry(lib, 'ucn_march_features')(
-            ctypes.byref(desc), *posts.geometry(rays, flip, spin), float(std_scale), N, S, int(lpb), layout,
+        _lib.check(posts.ray_call(
+            lib, 'ucn_march_features', ctypes.byref(desc), rays, flip, spin, slice(None), std_scale, mlp.warp, N, S, int(lpb), layout,
             feat.data_ptr(), coord.data_ptr(), tmean.data_ptr(), _lib.stream()))
         ctx.mlp, ctx.posts, ctx.cones, ctx.dims = mlp, posts, (rays, flip, spin), (N, S, float(std_scale), int(lpb))
         # the autocast step (half tables): the table gradient's row blocks accumulate in guaranteed-range fixed point (order-
@@ -85,9 +85,9 @@ class _FieldFeatures(torch.autograd.Function):
             else:
                 g, layout = g.contiguous(), 1
         ws = torch.empty(lib.ucn_march_features_backward_ws_floats(ctypes.byref(mlp.grid_field()), N, S), device=g.device)
-        _lib.check(ctx.posts.entry(lib, 'ucn_march_features_backward')(
-            ctypes.byref(mlp.grid_field()), *ctx.posts.geometry(*ctx.cones), std_scale, N, S, 0, layout | (_lib.BWD_FIXED_POINT if ctx.fixed else 0),
-            g.data_ptr(), grad.data_ptr(), ws.data_ptr(), _lib.stream()))
+        _lib.check(ctx.posts.ray_call(
+            lib, 'ucn_march_features_backward', ctypes.byref(mlp.grid_field()), *ctx.cones, slice(None), std_scale, mlp.warp, N, S, 0,
+            layout | (_lib.BWD_FIXED_POINT if ctx.fixed else 0), g.data_ptr(), grad.data_ptr(), ws.data_ptr(), _lib.stream()))
         return (grad,) + (None,) * 10
 
 
@@ -99,9 +99,9 @@ def scale_features(mlp, posts, rays, flip, spin, S, std_scale):
     lib = _lib.load()
     N, L = rays.N, mlp.encoder.num_levels
     out = torch.empty(N * S, L, device=rays.dev)
-    _lib.check(posts.entry(lib, 'ucn_march_scale_features')(
-        ctypes.byref(mlp.grid_field()), *posts.geometry(rays, flip, spin), float(std_scale), N, S, mlp.level_scale().data_ptr(), 1,
-        out.data_ptr(), _lib.stream()))
+    _lib.check(posts.ray_call(
+        lib, 'ucn_march_scale_features', ctypes.byref(mlp.grid_field()), rays, flip, spin, slice(None), std_scale, mlp.warp, N, S,
+        mlp.level_scale().data_ptr(), 1, out.data_ptr(), _lib.stream()))
     return out
 
 

@@ -152,12 +152,19 @@ class MLP(nn.Module):
                            use_diffuse_color=False, use_specular_tint=False, use_n_dot_v=False,
                            enable_pred_normals=False,
                            net_depth_viewdirs=2, skip_layer_dir=0, num_rgb_channels=3,
-                           warp_fn='contract', bottleneck_noise=0.0, density_noise=0.0)
+                           bottleneck_noise=0.0, density_noise=0.0)
         for k, want in unsupported.items():
             if getattr(self, k) != want:
                 raise NotImplementedError(
                     f"{type(self).__name__}.{k}={getattr(self, k)!r}: the HIP ray-march implements the shipped "
                     f"waymo.gin configuration only ({k}={want!r})")
+        if self.warp_fn not in ('contract', None):
+            # ref coord.py:93-96: track_linearize raises for anything else
+            raise NotImplementedError(
+                f"{type(self).__name__}.warp_fn={self.warp_fn!r}: supported are 'contract' (the unbounded scene contracted into "
+                "the grid) and None (a bounded scene inside [-1, 1]^3, the Gaussians reach the grid as they are)")
+        # the kernels' `warp` argument, resolved once: 1 = 'contract', 0 = None
+        self.warp = 1 if self.warp_fn == 'contract' else 0
         if not self.disable_density_normals and self.scale_featurization:
             raise NotImplementedError(
                 f"{type(self).__name__}: disable_density_normals=False with scale_featurization=True: the density gradient's term "
@@ -376,7 +383,7 @@ class MLP(nn.Module):
     @torch.no_grad()
     def predict_density(self, means, stds, rand=False, no_warp=False):
         """ref models.py:485-512.  means [..., G, 3], stds [..., G] -> (raw_density [...],
-        x [..., n_out], mean contracted coordinate [..., 3])."""
+        x [..., n_out], mean contracted coordinate [..., 3]).  A warp_fn = None field never warps: no_warp changes nothing there."""
         raw, x, coord, _, _, _ = self._evaluate(means, stds, None, no_warp, want_x=True, want_normals=False)
         return raw, x, coord
 
@@ -417,6 +424,7 @@ class MLP(nn.Module):
     def _evaluate(self, means, stds, viewdirs, no_warp, want_x, want_normals=True):
         # the split-f16 kernel composes the bottleneck away; the API that returns it uses the fp32 kernel's packed copy
         mode = 0 if (want_x and not self.disable_rgb) else int(self.mlp_mode)
+        no_warp = bool(no_warp) or not self.warp           # ref models.py:488: `if self.warp_fn is not None and not no_warp`
         lib = _lib.load()
         _lib.require_device(means, "means")
         prefix = means.shape[:-2]
@@ -753,7 +761,6 @@ class Model(nn.Module):
                 chunk = max(nerf_chunk, min(nerf_chunk * nerf_row // (S * planes(mlp) * C) // 256 * 256, 1 << 16))
             # ---- random draws and fenceposts (resample -> cone basis -> metric fenceposts of a warped raydist_fn)
             posts, flip, spin = ml.fenceposts(self, rays, i_level, S, dilation, train_frac, rand, posts, weights, st)
-            march_features = posts.entry(lib, 'ucn_march_features')
             # ---- outputs of the level
             density = torch.empty(N, S, device=dev)
             rgbs = None if is_prop else torch.empty(N, S, 3, device=dev)
@@ -806,13 +813,13 @@ class Model(nn.Module):
                     side.wait_event(mlp_done[i_pass % 2])             # the buffer's previous reader
                 if timed:
                     e0.record(fstream)
-                _lib.check(march_features(
-                    feat_desc, *posts.geometry(rays, flip, spin, sl), float(self.std_scale), n, S, int(self.levels_per_block), feat_layout,
-                    fb.data_ptr(), None if coord is None else coord[sl].data_ptr(), None, fstream.cuda_stream))
+                _lib.check(posts.ray_call(
+                    lib, 'ucn_march_features', feat_desc, rays, flip, spin, sl, self.std_scale, mlp.warp, n, S, int(self.levels_per_block),
+                    feat_layout, fb.data_ptr(), None if coord is None else coord[sl].data_ptr(), None, fstream.cuda_stream))
                 if level_scale is not None:          # the scale planes of this pass's n * S samples, behind its L grid planes
-                    _lib.check(posts.entry(lib, 'ucn_march_scale_features')(
-                        feat_desc, *posts.geometry(rays, flip, spin, sl), float(self.std_scale), n, S, level_scale.data_ptr(),
-                        feat_layout & 3, fb[L * n * S * C:].data_ptr(), fstream.cuda_stream))
+                    _lib.check(posts.ray_call(
+                        lib, 'ucn_march_scale_features', feat_desc, rays, flip, spin, sl, self.std_scale, mlp.warp, n, S,
+                        level_scale.data_ptr(), feat_layout & 3, fb[L * n * S * C:].data_ptr(), fstream.cuda_stream))
                 if timed:
                     e1.record(fstream)
                 if overlap:
