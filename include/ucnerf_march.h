@@ -325,6 +325,17 @@ int ucn_march_density_grad(const ucn_field_t *f, const float *fenceposts, const 
 int ucn_points_density_grad(const ucn_field_t *f, const float *means, const float *stds, uint32_t B, uint32_t G, int warp,
                             const float *gfeat, float *raw_grad_out, float *normals_out, ucn_stream_t stream);
 
+/* ------------------------------------------------- predicted normals (added within ABI 32; ref: models.py:442-444, :569-578,
+ * MLP.enable_pred_normals = True)
+ * grad_pred = normal_layer(x) over the density layer's output x = Wd1 h + bd1, h = relu(W0 features + b0), composed as A h + c with
+ * A = Wn Wd1 [3,64] and c = Wn bd1 + bn [3] (DEVICE, float32, formed by the caller once per call); normals_pred = -grad_pred /
+ * max(|grad_pred|, float32 eps).  h is recomputed in fp32 from w_d0 / b_d0 (the unpacked weights; w_d0 [64][(num_levels +
+ * n_scale_planes) * level_dim], i.e. zero-padded over the scale planes' padding channels) in every mlp_mode.  One call after the
+ * level's ucn_field_mlp, on the same stream.  features: [num_levels + n_scale_planes][N*S][level_dim] as ucn_march_features (and
+ * ucn_march_scale_features behind it) wrote them, layout 0 / 2: b = ray*S + s / b = s*N + ray.  Outputs [N,S,3], always [ray][s]. */
+int ucn_pred_normals(const ucn_field_t *f, const float *A, const float *c, const float *features, uint32_t N, uint32_t S, int layout,
+                     float *grad_pred_out, float *normals_pred_out, ucn_stream_t stream);
+
 /* ------------------------------------------------- the ray path with the field's warp as an argument (added within ABI 32;
  * ref: MLP.warp_fn, models.py:392 and :488-494; coord.py:93-96 track_linearize knows 'contract' and None)
  * warp = 1: 'contract' -- each call below is then the entry point of the same name without `_warp` (or its `_tdist` sibling), which
@@ -810,6 +821,13 @@ int ucn_data_loss_ex(const float *const *rgb_levels_host, uint32_t L, const floa
  * o / (o + 1e-5)) / N.  L <= 4; one launch each way, terms formed and added in double. */
 int ucn_opacity_loss(const float *const *acc_levels_host /*[L] device pointers, each [N]*/, uint32_t L, uint32_t N, float mult,
                      float *loss_out /*[1]*/, const float *g /*[1]|NULL*/, float *const *g_acc_levels_host, ucn_stream_t stream);
+/* ucn_neg_normalize (added within ABI 32; models.py:574): out [M,3] = -g / max(|g|, float32 eps) (dn NULL), or with dn [M,3] the
+ * backward: out = -(dn - n (n . dn)) / |g| above the clamp, -dn / eps below it.  The three-term sums are formed in double. */
+int ucn_neg_normalize(const float *g /*[M,3]*/, uint64_t M, const float *dn /*[M,3]|NULL*/, float *out /*[M,3]*/, ucn_stream_t stream);
+/* ucn_orientation_loss (added within ABI 32; train_utils.py:282-298, one level): g_loss NULL -> out [N] = sum_s w_s max(0, n_s . (-v))^2
+ * per ray, summed in double; g_loss [N] -> out [N,S] = d / d w, dn_out [N,S,3] = d / d n of sum_ray g_loss[ray] loss[ray].  No atomics. */
+int ucn_orientation_loss(const float *w /*[N,S]*/, const float *n /*[N,S,3]*/, const float *viewdirs /*[N,3]*/, uint32_t N, uint32_t S,
+                         const float *g_loss /*[N]|NULL*/, float *out, float *dn_out /*[N,S,3]|NULL*/, ucn_stream_t stream);
 /* ucn_sky_loss (train_utils.py:149-157): sum_l mean BCE(clip(acc_l, 1e-3, 0.999), 1 - sky_segs) */
 int ucn_sky_loss(const float *const *acc_levels_host /*[L] device pointers, each [N]*/, uint32_t L, const float *sky_segs /*[N]*/, uint32_t N,
                  float *loss_out /*[1]*/, const float *g /*[1]|NULL*/, float *const *g_acc_levels_host, ucn_stream_t stream);

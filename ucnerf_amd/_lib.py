@@ -112,6 +112,10 @@ SIGNATURES = {
                                     c_u32, c_u32, c_i32, c_vp, c_vp, c_vp, c_vp],
     "ucn_cast_probe_warp": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i32, c_u32, c_u32, c_vp, c_vp],
     "ucn_points_density_grad": [ctypes.POINTER(UcnField), c_vp, c_vp, c_u32, c_u32, c_i32, c_vp, c_vp, c_vp, c_vp],
+    # predicted normals (MLP.enable_pred_normals; added within ABI 32): the head's kernel and the training graph's two nodes
+    "ucn_pred_normals": [ctypes.POINTER(UcnField), c_vp, c_vp, c_vp, c_u32, c_u32, c_i32, c_vp, c_vp, c_vp],
+    "ucn_neg_normalize": [c_vp, c_u64, c_vp, c_vp, c_vp],
+    "ucn_orientation_loss": [c_vp, c_vp, c_vp, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp],
     "ucn_field_dir_floats": [ctypes.POINTER(UcnField), c_u32],
     "ucn_field_dir_bias": [ctypes.POINTER(UcnField), c_vp, c_u32, c_vp, c_vp],
     "ucn_field_mlp": [ctypes.POINTER(UcnField), c_vp, c_u32, c_u32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp],

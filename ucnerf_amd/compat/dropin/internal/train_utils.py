@@ -10,6 +10,7 @@ this repo's device implementations of the same name and signature (train.py:102,
     distortion_loss         ucn_distortion_loss, O(S) per ray
     hash_decay_loss         reads ray_history[...]['loss_hash_decay'] (ucn_hash_decay inside the model)
     sky_loss, transformIdentityLoss
+    orientation_loss        ucn_orientation_loss on the predicted normals (orientation_loss_target = 'normals_pred'), one launch per level
     clip_gradients          one launch for every gradient's nan_to_num
     create_optimizer        FusedAdam (a torch.optim.Adam subclass with torch's state layout)
 """
@@ -28,4 +29,4 @@ upstream = _up
 
 from ucnerf_amd.internal.train_utils import (FusedAdam, LazyStats, anti_interlevel_loss, clip_gradients,  # noqa: E402,F401
                                              compute_data_loss, create_optimizer, distortion_loss, hash_decay_loss,
-                                             interlevel_loss, opacity_loss, sky_loss, transformIdentityLoss)
+                                             interlevel_loss, opacity_loss, orientation_loss, sky_loss, transformIdentityLoss)

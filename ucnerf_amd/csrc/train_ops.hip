@@ -790,3 +790,89 @@ extern "C" int ucn_ray_film_backward(const void *gy, const void *x, const float 
     UCN_LAUNCH_CHECK("ray_film_backward");
     return 0;
 }
+
+// ---- predicted normals in the training graph (models.py:569-578, train_utils.py:282-298) ------------------------------
+namespace {
+
+// n = -g / max(|g|, eps) (ref_utils.l2_normalize = F.normalize(eps = float32 eps), negated) for M vectors, one per thread.
+// Backward: above the clamp n = -g / r, so dg = -(dn - n (n . dn)) / r; below it n = -g / eps and dg = -dn / eps.  The three-term sums
+// (|g|^2, n . dn) are formed in double and rounded once.
+template <bool BWD>
+__global__ __launch_bounds__(256) void k_neg_normalize(const float *__restrict__ g, const float *__restrict__ dn, size_t M,
+                                                       float *__restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= M) return;
+    const double g0 = g[i * 3], g1 = g[i * 3 + 1], g2 = g[i * 3 + 2];
+    const double r = sqrt((g0 * g0 + g1 * g1) + g2 * g2);
+    const double eps = (double)UCN_EPS;
+    const double den = r > eps ? r : eps;
+    const double n0 = -(g0 / den), n1 = -(g1 / den), n2 = -(g2 / den);
+    if (!BWD) {
+        out[i * 3] = (float)n0; out[i * 3 + 1] = (float)n1; out[i * 3 + 2] = (float)n2;
+        return;
+    }
+    const double d0 = dn[i * 3], d1 = dn[i * 3 + 1], d2 = dn[i * 3 + 2];
+    if (r > eps) {
+        const double nd = (n0 * d0 + n1 * d1) + n2 * d2;
+        out[i * 3] = (float)(-(d0 - n0 * nd) / r); out[i * 3 + 1] = (float)(-(d1 - n1 * nd) / r); out[i * 3 + 2] = (float)(-(d2 - n2 * nd) / r);
+    } else {
+        out[i * 3] = (float)(-d0 / eps); out[i * 3 + 1] = (float)(-d1 / eps); out[i * 3 + 2] = (float)(-d2 / eps);
+    }
+}
+
+// Orientation term of one level (train_utils.py:282-298): loss[ray] = sum_s w_s max(0, n_s . (-v))^2.  One wave per ray, a lane takes the
+// samples s = lane, lane + 64, ...; the per-ray sum is formed in double (lane partials, then the wave sum).  Backward: every sample's
+// dw_s = g max(0, d_s)^2 and dn_s = g w_s 2 max(0, d_s) (-v) are its thread's own: no atomics.
+template <bool BWD>
+__global__ __launch_bounds__(256) void k_orientation(const float *__restrict__ w, const float *__restrict__ n, const float *__restrict__ v,
+                                                     uint32_t N, uint32_t S, const float *__restrict__ g_loss, float *__restrict__ out,
+                                                     float *__restrict__ dn_out) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t ray = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (ray >= N) return;
+    const float v0 = -v[(size_t)ray * 3], v1 = -v[(size_t)ray * 3 + 1], v2 = -v[(size_t)ray * 3 + 2];
+    const float g = BWD ? g_loss[ray] : 0.0f;
+    double acc = 0.0;
+    for (uint32_t s = lane; s < S; s += 64u) {
+        const size_t o = (size_t)ray * S + s;
+        const float d = fmaxf((n[o * 3] * v0 + n[o * 3 + 1] * v1) + n[o * 3 + 2] * v2, 0.0f);
+        const float ws = w[o];
+        if (BWD) {
+            out[o] = g * (d * d);
+            const float k = g * ws * (2.0f * d);
+            dn_out[o * 3] = k * v0; dn_out[o * 3 + 1] = k * v1; dn_out[o * 3 + 2] = k * v2;
+        } else {
+            acc += (double)ws * ((double)d * (double)d);
+        }
+    }
+    if (!BWD) {
+        acc = wave_sum_dpp<double>(acc);
+        if (lane == 0) out[ray] = (float)acc;
+    }
+}
+
+}  // namespace
+
+extern "C" int ucn_neg_normalize(const float *g, uint64_t M, const float *dn, float *out, ucn_stream_t stream) {
+    if (M == 0) return 0;
+    UCN_REQUIRE(g && out, "neg_normalize: null pointer argument");
+    UCN_REQUIRE(M <= 0xFFFFFF00ull, "neg_normalize: too many vectors in one call (%llu)", (unsigned long long)M);
+    const dim3 grid(ucn_div_up(M, 256));
+    if (dn) hipLaunchKernelGGL(k_neg_normalize<true>, grid, dim3(256), 0, (hipStream_t)stream, g, dn, (size_t)M, out);
+    else hipLaunchKernelGGL(k_neg_normalize<false>, grid, dim3(256), 0, (hipStream_t)stream, g, dn, (size_t)M, out);
+    UCN_LAUNCH_CHECK("neg_normalize");
+    return 0;
+}
+
+extern "C" int ucn_orientation_loss(const float *w, const float *n, const float *viewdirs, uint32_t N, uint32_t S, const float *g_loss,
+                                    float *out, float *dn_out, ucn_stream_t stream) {
+    if (N == 0) return 0;
+    UCN_REQUIRE(w && n && viewdirs && out, "orientation_loss: null pointer argument");
+    UCN_REQUIRE((g_loss == nullptr) == (dn_out == nullptr), "orientation_loss: g_loss and dn_out come together (the backward)");
+    UCN_REQUIRE(S >= 1, "orientation_loss: samples per ray must be at least 1");
+    const dim3 grid(ucn_div_up(N, 4));
+    if (g_loss) hipLaunchKernelGGL(k_orientation<true>, grid, dim3(256), 0, (hipStream_t)stream, w, n, viewdirs, N, S, g_loss, out, dn_out);
+    else hipLaunchKernelGGL(k_orientation<false>, grid, dim3(256), 0, (hipStream_t)stream, w, n, viewdirs, N, S, g_loss, out, dn_out);
+    UCN_LAUNCH_CHECK("orientation_loss");
+    return 0;
+}

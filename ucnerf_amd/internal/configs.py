@@ -17,3 +17,8 @@ class Config:
     near: float = 0.                        # waymo.gin:2
     far: float = 8.                         # waymo.gin:3
     render_ray_tile: int = 8                # not in the reference: render_image marches T x T pixel blocks per wave (1 = row order)
+    orientation_loss_mult: float = 0.0      # configs.py:81
+    orientation_coarse_loss_mult: float = 0.0   # configs.py:82
+    orientation_loss_target: str = 'normals_pred'   # configs.py:84: 'normals' or 'normals_pred'; only 'normals_pred' is built
+    predicted_normal_loss_mult: float = 0.0  # configs.py:85 (refused when non-zero: DESIGN.md 7d)
+    predicted_normal_coarse_loss_mult: float = 0.0   # configs.py:87 (the same)

@@ -249,14 +249,27 @@ def density_normals(mlp, posts, rays, flip, spin, sl, n, S, std_scale, layout, f
                               feat.data_ptr(), raw_grad[sl].data_ptr(), normals[sl].data_ptr(), stream))
 
 
+def pred_normals(desc, head, feat, sl, n, S, layout, grad_pred, normals_pred, stream):
+    """models.py:569-578 for the n rays `sl` of a level, after its dense layers, on `stream`: ucn_pred_normals reads the pass's feature
+    buffer `feat` ([L + scale planes][n*S][C], layout 0 or 2 as the gather wrote it) and fills grad_pred[sl] and normals_pred[sl]
+    ([N, S, 3]).  desc: the level's mlp.field() (its unpacked density_layer.0); head: mlp.pred_head().  No autograd graph."""
+    A, c = head
+    _lib.check(_lib.load().ucn_pred_normals(ctypes.byref(desc), A.data_ptr(), c.data_ptr(), feat.data_ptr(), n, S, layout,
+                                            grad_pred[sl].data_ptr(), normals_pred[sl].data_ptr(), stream))
+
+
 # ---- result dictionaries (the keys of ref models.py:262-324) -------------------------------------------------------------
-def rendering_entry(rgb, depth, acc, weights, extras, prefix, sdist=None, rgbs=None, n_vis=16, normals=None):
+def rendering_entry(rgb, depth, acc, weights, extras, prefix, sdist=None, rgbs=None, n_vis=16, normals=None, normals_pred=None):
     """rgb [N, 3], depth [N], acc [N], weights [N, S]; with extras [N, 4] (compute_extras: distance mean, 5 %, median, 95 %) also the
     'ray_*' keys: the first n_vis rays' fenceposts, weights and colours (rgbs None, a proposal level: zeros until `broadcast_final`)."""
     N, S = weights.shape
     r = dict(rgb=rgb.reshape(prefix + (3,)), depth=depth.reshape(prefix), acc=acc.reshape(prefix))
     if extras is not None and normals is not None:          # render.py:218-222: alpha-composited like the colours, no background term
         r['normals'] = (weights.detach()[..., None] * normals).sum(dim=-2).reshape(prefix + (3,))
+    # the same for the predicted normals (a key that starts with 'normals', models.py:279-283).  The rendered key carries NO gradient, in the
+    # training graph too (the reference composites it with the graph attached; no loss reads the rendering: train_utils reads the history)
+    if extras is not None and normals_pred is not None:
+        r['normals_pred'] = (weights.detach()[..., None] * normals_pred.detach()).sum(dim=-2).reshape(prefix + (3,))
     if extras is not None:
         for j, k in enumerate(('distance_mean', 'distance_percentile_5', 'distance_median', 'distance_percentile_95')):
             r[k] = extras[:, j].reshape(prefix)
@@ -274,11 +287,13 @@ def broadcast_final(renderings):
         r['ray_rgbs'] = final[:, None, :].expand(r['ray_rgbs'].shape)
 
 
-def history_entry(coord, density, rgbs, sdist, weights, prefix, raw_grad=None, normals=None):
+def history_entry(coord, density, rgbs, sdist, weights, prefix, raw_grad=None, normals=None, grad_pred=None, normals_pred=None):
     """coord [N, S, 3], density [N, S], rgbs [N, S, 3] or None (zeros), sdist [N, S+1], weights [N, S]."""
     N, S = weights.shape
     rgb = torch.zeros(N, S, 3, device=weights.device) if rgbs is None else rgbs
     return dict(coord=coord.reshape(prefix + (S, 3)), density=density.reshape(prefix + (S,)), rgb=rgb.reshape(prefix + (S, 3)),
-                raw_grad_density=None if raw_grad is None else raw_grad.reshape(prefix + (S, 3)), grad_pred=None,
-                normals=None if normals is None else normals.reshape(prefix + (S, 3)), normals_pred=None, roughness=None,
+                raw_grad_density=None if raw_grad is None else raw_grad.reshape(prefix + (S, 3)),
+                grad_pred=None if grad_pred is None else grad_pred.reshape(prefix + (S, 3)),
+                normals=None if normals is None else normals.reshape(prefix + (S, 3)),
+                normals_pred=None if normals_pred is None else normals_pred.reshape(prefix + (S, 3)), roughness=None,
                 sdist=sdist.reshape(prefix + (S + 1,)).clone(), weights=weights.reshape(prefix + (S,)).clone())

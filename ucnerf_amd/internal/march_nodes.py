@@ -240,6 +240,29 @@ class _CompositeRays(torch.autograd.Function):
         return g_density, g_rgbs, g_gain, None, None, None, None, None
 
 
+class _NegNormalize(torch.autograd.Function):
+    """models.py:574 `-ref_utils.l2_normalize(grad_pred)`: n = -g / max(|g|, float32 eps) over [..., 3] as one HIP launch each way
+    (`ucn_neg_normalize`); backward -(dn - n (n . dn)) / |g| above the clamp, -dn / eps below it."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, g):
+        g = g.contiguous()
+        out = torch.empty_like(g)
+        _lib.check(_lib.load().ucn_neg_normalize(g.data_ptr(), g.numel() // 3, None, out.data_ptr(), _lib.stream()))
+        ctx.save_for_backward(g)
+        return out
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, dn):
+        (g,) = ctx.saved_tensors
+        dn = dn.float().contiguous()
+        out = torch.empty_like(g)
+        _lib.check(_lib.load().ucn_neg_normalize(g.data_ptr(), g.numel() // 3, dn.data_ptr(), out.data_ptr(), _lib.stream()))
+        return out
+
+
 class _HashDecay(torch.autograd.Function):
     """models.py:297-306 as one pass over the table forward and one backward (`ucn_hash_decay`); the per-level slices of
     the reference's formulation cost 16 full-table zero-fills and adds in autograd, the torch form of the weighted sum

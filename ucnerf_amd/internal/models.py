@@ -12,7 +12,8 @@ Supported configuration = the reference's shipped one (configs/waymo.gin): disab
 no reflections / diffuse / IDE, plus GLO appearance codes (num_glo_features > 0; DESIGN.md "GLO") and every
 ray-distance curve of coord.construct_ray_warps (raydist_fn None, 'piecewise', 'power_transformation' or a gin-bound
 torch.reciprocal / log / exp / sqrt / square; DESIGN.md "Ray-distance curves") and the featurized grid scale
-(MLP.scale_featurization) and analytic density normals (MLP.disable_density_normals = False).
+(MLP.scale_featurization) and analytic density normals (MLP.disable_density_normals = False) and the
+predicted-normal head (MLP.enable_pred_normals).
 Anything else raises at construction.
 In eval mode or with gradients disabled forward is the fused inference march; a model in training mode
 with gradients enabled routes to internal/train_graph.py `march_train` (same kernels for resampling and featurisation, HIP
@@ -150,7 +151,6 @@ class MLP(nn.Module):
         set_kwargs(self, kwargs)
         unsupported = dict(use_reflections=False, use_directional_enc=False, enable_pred_roughness=False,
                            use_diffuse_color=False, use_specular_tint=False, use_n_dot_v=False,
-                           enable_pred_normals=False,
                            net_depth_viewdirs=2, skip_layer_dir=0, num_rgb_channels=3,
                            bottleneck_noise=0.0, density_noise=0.0)
         for k, want in unsupported.items():
@@ -170,6 +170,16 @@ class MLP(nn.Module):
                 f"{type(self).__name__}: disable_density_normals=False with scale_featurization=True: the density gradient's term "
                 "through the scale features (their erf damping depends on the position outside the unit ball) is not built "
                 "(DESIGN.md 7d)")
+        if self.enable_pred_normals and not self.disable_density_normals:
+            raise NotImplementedError(
+                f"{type(self).__name__}: enable_pred_normals=True with disable_density_normals=False: the only consumer of both at "
+                "once is predicted_normal_loss, which differentiates the density normals, and their second-order path is not built "
+                "(DESIGN.md 7h)")
+        if self.enable_pred_normals and self.disable_rgb:
+            raise NotImplementedError(
+                f"{type(self).__name__}: enable_pred_normals=True with disable_rgb=True: the reference applies normal_layer = "
+                "Linear(bottleneck_width, 3) to the 1-wide density output there (models.py:440-444) and fails in forward; give the "
+                "field its colour layers (disable_rgb=False)")
         self.grid_num_levels = int(np.log(self.grid_disired_resolution / self.grid_base_resolution)
                                    / np.log(self.grid_level_interval)) + 1
         self.encoder = GridEncoder(input_dim=3, num_levels=self.grid_num_levels, level_dim=self.grid_level_dim,
@@ -181,6 +191,8 @@ class MLP(nn.Module):
             last_dim += self.encoder.num_levels
         self.density_layer = nn.Sequential(nn.Linear(last_dim, 64), nn.ReLU(),
                                            nn.Linear(64, 1 if self.disable_rgb else self.bottleneck_width))
+        if self.enable_pred_normals:                 # ref models.py:442-444: registered here (the state dict's key order)
+            self.normal_layer = nn.Linear(self.bottleneck_width, 3)
         self.dim_dir_enc = 3 + 6 * self.deg_view
         if not self.disable_rgb:
             last_dim_rgb = self.bottleneck_width + self.dim_dir_enc
@@ -201,7 +213,26 @@ class MLP(nn.Module):
             self.rgb_layer = nn.Linear(last_dim_rgb, self.num_rgb_channels)
         self._fields = {}          # (mlp_mode, glo fold) -> (key, ucn_field_t, packed weight stream): one packed buffer each
 
-    _UNPICKLED = ('_fields', '_grid_desc', '_grid_desc_key', '_glo_fold', '_level_scale')
+    _UNPICKLED = ('_fields', '_grid_desc', '_grid_desc_key', '_glo_fold', '_level_scale', '_pred_head')
+
+    # ---- predicted normals (ref models.py:442-444, :569-578) -------------------------
+    def pred_head(self):
+        """(A = Wn Wd1 [3, 64], c = Wn bd1 + bn [3]), float32 on the device: normal_layer composed with density_layer.2, what
+        ucn_pred_normals applies to the hidden layer (the inference kernels never materialise the bottleneck).  Two small fp32
+        products, recomputed only when one of the four parameters changed."""
+        nl, d1 = self.normal_layer, self.density_layer[2]
+        ps = [nl.weight, nl.bias, d1.weight, d1.bias]
+        for p in ps:
+            _lib.require_device(p, f"{type(self).__name__} parameter")
+        key = tuple((p.data_ptr(), p._version) for p in ps)
+        hit = getattr(self, '_pred_head', None)
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        with torch.no_grad(), torch.autocast('cuda', enabled=False):
+            Wn = nl.weight.float()
+            out = ((Wn @ d1.weight.float()).contiguous(), (Wn @ d1.bias.float() + nl.bias.float()).contiguous())
+        self._pred_head = (key, out)
+        return out
 
     # ---- scale featurization (ref models.py:436-437, :497-506; DESIGN.md 7c) ---------------------
     def scale_planes(self):
@@ -395,15 +426,15 @@ class MLP(nn.Module):
         node (_ColourMLPGlo) on the fp32 kernel's bottleneck, without gradients."""
         if glo_vec is not None and self.uses_glo() and viewdirs is not None:
             return self._forward_glo(means, stds, viewdirs, glo_vec, no_warp)
-        _, _, coord, density, rgb, (raw_grad, normals) = self._evaluate(means, stds, viewdirs, no_warp, want_x=False)
+        _, _, coord, density, rgb, (raw_grad, normals, grad_pred, normals_pred) = self._evaluate(means, stds, viewdirs, no_warp, want_x=False)
         if self.disable_rgb or viewdirs is None:
             rgb = torch.zeros(density.shape + (3,), device=density.device)
-        return dict(coord=coord, density=density, rgb=rgb, raw_grad_density=raw_grad, grad_pred=None, normals=normals,
-                    normals_pred=None, roughness=None)
+        return dict(coord=coord, density=density, rgb=rgb, raw_grad_density=raw_grad, grad_pred=grad_pred, normals=normals,
+                    normals_pred=normals_pred, roughness=None)
 
     def _forward_glo(self, means, stds, viewdirs, glo_vec, no_warp):
         from .heads_f32 import _ColourMLPGlo
-        raw, x, coord, _, _, (raw_grad, normals) = self._evaluate(means, stds, None, no_warp, want_x=True)
+        raw, x, coord, _, _, (raw_grad, normals, grad_pred, normals_pred) = self._evaluate(means, stds, None, no_warp, want_x=True)
         prefix = raw.shape
         vd = _f32(viewdirs, -1, 3)
         N = vd.shape[0]
@@ -418,8 +449,8 @@ class MLP(nn.Module):
                                        l1.weight, l1.bias, N, B // N)
             logits = torch.nn.functional.linear(h, self.rgb_layer.weight, self.rgb_layer.bias)
         rgb = rgb_activation(self, logits)
-        return dict(coord=coord, density=density, rgb=rgb.reshape(prefix + (3,)), raw_grad_density=raw_grad, grad_pred=None,
-                    normals=normals, normals_pred=None, roughness=None)
+        return dict(coord=coord, density=density, rgb=rgb.reshape(prefix + (3,)), raw_grad_density=raw_grad, grad_pred=grad_pred,
+                    normals=normals, normals_pred=normals_pred, roughness=None)
 
     def _evaluate(self, means, stds, viewdirs, no_warp, want_x, want_normals=True):
         # the split-f16 kernel composes the bottleneck away; the API that returns it uses the fp32 kernel's packed copy
@@ -463,7 +494,12 @@ class MLP(nn.Module):
             rgb = torch.empty(B, 3, device=dev)
         _lib.check(lib.ucn_field_mlp(ctypes.byref(d), feat.data_ptr(), B, spr, 0, _lib.ptr(dirb), density.data_ptr(),
                                      _lib.ptr(rgb), _lib.ptr(x), st))
-        nrm = (None, None)
+        nrm = (None, None, None, None)
+        if want_normals and self.enable_pred_normals:
+            # models.py:569-578: the head on the hidden layer, before any GLO modulation; the MLP left the features as they were
+            grad_pred, normals_pred = torch.empty(B, 1, 3, device=dev), torch.empty(B, 1, 3, device=dev)
+            ml.pred_normals(d, self.pred_head(), feat, slice(None), B, 1, 0, grad_pred, normals_pred, st)
+            nrm = (None, None, grad_pred.reshape(prefix + (3,)), normals_pred.reshape(prefix + (3,)))
         if want_normals and not self.disable_density_normals:
             # models.py:550-567: after the field MLP, on the same stream; the feature buffer is free and becomes gfeat in place
             nd = self.normals_field()
@@ -471,7 +507,7 @@ class MLP(nn.Module):
             _lib.check(lib.ucn_density_feature_grad(ctypes.byref(nd), feat.data_ptr(), B, feat.data_ptr(), st))
             _lib.check(lib.ucn_points_density_grad(ctypes.byref(nd), m.data_ptr(), s.data_ptr(), B, G, 0 if no_warp else 1,
                                                    feat.data_ptr(), raw_grad.data_ptr(), normals.data_ptr(), st))
-            nrm = (raw_grad.reshape(prefix + (3,)), normals.reshape(prefix + (3,)))
+            nrm = (raw_grad.reshape(prefix + (3,)), normals.reshape(prefix + (3,)), None, None)
         # raw (pre-activation) density: softplus is inverted only for API parity of predict_density
         raw = None
         if want_x:
@@ -570,15 +606,32 @@ class Model(nn.Module):
         for k, want in dict(single_mlp=False, distinct_prop=True, use_viewdirs=True).items():
             if getattr(self, k) != want:
                 raise NotImplementedError(f"Model.{k}={getattr(self, k)!r} is outside the shipped waymo.gin path")
-        for k in ('orientation_loss_mult', 'predicted_normal_loss_mult'):
-            # the only consumers of the normals' own gradient (the reference's create_graph=True, models.py:559): not built,
-            # the normals are returned detached; both default to 0 (configs.py:81,85)
+        for k in ('predicted_normal_loss_mult', 'predicted_normal_coarse_loss_mult'):
+            # the consumer of the density normals' own gradient (the reference's create_graph=True, models.py:559): not built,
+            # the normals are returned detached; both default to 0 (configs.py:85,87)
             if getattr(config, k, 0):
                 raise NotImplementedError(f"config.{k}={getattr(config, k)!r}: the second-order path through the density normals "
                                           "is not built (normals are returned detached)")
         self.nerf_mlp = NerfMLP(num_glo_features=self.num_glo_features, num_glo_embeddings=self.num_glo_embeddings)
         for i in range(self.num_levels - 1):
             self.register_module(f'prop_mlp_{i}', PropMLP(grid_disired_resolution=self.prop_desired_grid_size[i]))
+        for k in ('orientation_loss_mult', 'orientation_coarse_loss_mult'):
+            # train_utils.orientation_loss reads every level's target (train_utils.py:282-298).  On 'normals_pred' (the default,
+            # configs.py:84) it needs first-order gradients only and every level's field must carry the head; on 'normals' it would
+            # differentiate the density normals, which are returned detached
+            if not getattr(config, k, 0):
+                continue
+            target = getattr(config, 'orientation_loss_target', 'normals_pred')
+            if target != 'normals_pred':
+                raise NotImplementedError(f"config.{k}={getattr(config, k)!r} with orientation_loss_target={target!r}: the second-order "
+                                          "path through the density normals is not built (normals are returned detached); the "
+                                          "supported target is 'normals_pred'")
+            fields = [self.nerf_mlp] + [self.get_submodule(f'prop_mlp_{i}') for i in range(self.num_levels - 1)]
+            missing = [type(m).__name__ for m in fields if not m.enable_pred_normals]
+            if missing:
+                raise NotImplementedError(f"config.{k}={getattr(config, k)!r}: the orientation loss reads normals_pred of every level, "
+                                          f"but {', '.join(missing)} were built without enable_pred_normals (for a proposal level: "
+                                          "PropMLP.disable_rgb = False, PropMLP.enable_pred_normals = True)")
         if self.num_glo_features > 0 and not getattr(config, 'zero_glo', False):
             # ref models.py:73-75: one appearance code per training image, looked up by batch['cam_idx']
             self.glo_vecs = nn.Embedding(self.num_glo_embeddings, self.num_glo_features)
@@ -648,6 +701,8 @@ class Model(nn.Module):
         if mlp.scale_featurization:                # the bf16 inference kernels read grid planes only: fp32-class path
             return None
         if not mlp.disable_density_normals:        # the normals pass reads fp32 features of the fp32 table: fp32-class path
+            return None
+        if mlp.enable_pred_normals:                # the head's kernel reads the fp32 feature buffer: fp32-class path
             return None
         from .train_graph import heads_route
         emb = mlp.encoder.embeddings
@@ -730,8 +785,8 @@ class Model(nn.Module):
             def run(fb, sl, r0, n):
                 _lib.check(lib.ucn_field_mlp(
                     ctypes.byref(desc), fb.data_ptr(), n * S, S, rf | co,
-                    None if is_prop else dirb[r0 * dir_row:].data_ptr(),
-                    density[sl].data_ptr(), None if is_prop else rgbs[sl].data_ptr(), None, st))
+                    None if rgbs is None else dirb[r0 * dir_row:].data_ptr(),
+                    density[sl].data_ptr(), None if rgbs is None else rgbs[sl].data_ptr(), None, st))
         return run
 
     def _march(self, rand, batch, train_frac, compute_extras, eval_camidx, want_history):
@@ -763,7 +818,13 @@ class Model(nn.Module):
             posts, flip, spin = ml.fenceposts(self, rays, i_level, S, dilation, train_frac, rand, posts, weights, st)
             # ---- outputs of the level
             density = torch.empty(N, S, device=dev)
-            rgbs = None if is_prop else torch.empty(N, S, 3, device=dev)
+            # colours: the NeRF level's, and those of a proposal field built with its colour layers (PropMLP.disable_rgb = False; the
+            # reference composites them like the last level's, models.py:221-283)
+            rgbs = None if mlp.disable_rgb else torch.empty(N, S, 3, device=dev)
+            level_dirb = dirb
+            if is_prop and rgbs is not None:
+                level_dirb = torch.empty(lib.ucn_field_dir_floats(ctypes.byref(desc), N), device=dev)
+                _lib.check(lib.ucn_field_dir_bias(ctypes.byref(desc), rays.vd.data_ptr(), N, level_dirb.data_ptr(), st))
             weights = torch.empty(N, S, device=dev)
             main = torch.empty(N, 5, device=dev)
             extras = torch.empty(N, 4, device=dev) if compute_extras else None
@@ -773,6 +834,11 @@ class Model(nn.Module):
             raw_grad = torch.empty(N, S, 3, device=dev) if want_normals else None
             normals = torch.empty(N, S, 3, device=dev) if want_normals else None
             normals_field = mlp.normals_field() if want_normals else None          # once per level, not per pass
+            # predicted normals: for every sample (compacted or not), when something returns them
+            want_pred = mlp.enable_pred_normals and (want_history or compute_extras)
+            grad_pred = torch.empty(N, S, 3, device=dev) if want_pred else None
+            normals_pred = torch.empty(N, S, 3, device=dev) if want_pred else None
+            pred_head = mlp.pred_head() if want_pred else None                     # once per level, not per pass
             nc = min(chunk, N)
             feat = torch.empty(planes(mlp) * nc * S * C, device=dev)
             level_scale = mlp.level_scale() if mlp.scale_featurization else None
@@ -785,7 +851,7 @@ class Model(nn.Module):
             overlap = bool(self.overlap_streams) and N > chunk
             co = _lib.LAUNCH_CORESIDENT if (overlap and not is_prop and self.overlap_streams != 2) else 0     # launch shapes that share a CU (2: plain shapes, tails only)
             compact = (not is_prop) and (not want_history) and self.compact_min_weight > 0 and mlp.mlp_mode == 1 and mixed is None
-            run_mlp = self._mlp_route(mlp=mlp, is_prop=is_prop, S=S, desc=desc, mixed=mixed, rays=rays, posts=posts, dirb=dirb, co=co,
+            run_mlp = self._mlp_route(mlp=mlp, is_prop=is_prop, S=S, desc=desc, mixed=mixed, rays=rays, posts=posts, dirb=level_dirb, co=co,
                                       compact=compact, density=density, rgbs=rgbs, weights=weights, main=main, nc=nc)
             feat_desc = ctypes.byref(desc if mixed is None else mixed['desc'])
             feat_layout = ((2 if self.rays_fastest else 0) | co) if mixed is None else (2 | mixed['table_flag'] | (mixed['feat_flag'] if not is_prop else 0))
@@ -833,6 +899,8 @@ class Model(nn.Module):
                     # (with _prof set, e2 below closes after it: the pass's "MLP" time then includes the normals pass)
                     ml.density_normals(mlp, posts, rays, flip, spin, sl, n, S, self.std_scale, feat_layout & 3, fb, raw_grad, normals, st,
                                        field=normals_field)
+                if want_pred:                         # behind the MLP, on its stream: reads the pass's feature buffer, which the MLP left intact
+                    ml.pred_normals(desc, pred_head, fb, sl, n, S, feat_layout & 3, grad_pred, normals_pred, st)
                 if overlap:
                     mlp_done[i_pass % 2] = torch.cuda.Event()
                     mlp_done[i_pass % 2].record(cur)
@@ -845,9 +913,10 @@ class Model(nn.Module):
             bg, ray_bg = ml.background(self, rays, i_level, rand)
             ml.composite(posts, density, rgbs, rays.d, gain, ray_bg, bg, self.opaque_background, weights, main, extras, st)
             renderings.append(ml.rendering_entry(main[:, 0:3], main[:, 3], main[:, 4], weights, extras, prefix, posts.sdist, rgbs,
-                                                 getattr(cfg, 'vis_num_rays', 16), normals=normals))
+                                                 getattr(cfg, 'vis_num_rays', 16), normals=normals, normals_pred=normals_pred))
             if want_history:
-                ray_history.append(ml.history_entry(coord, density, rgbs, posts.sdist, weights, prefix, raw_grad, normals))
+                ray_history.append(ml.history_entry(coord, density, rgbs, posts.sdist, weights, prefix, raw_grad, normals,
+                                                    grad_pred=grad_pred, normals_pred=normals_pred))
 
         if compute_extras:                                             # ref models.py:313-324
             ml.broadcast_final(renderings)

@@ -32,7 +32,7 @@ from .head_pack import (_acc_vec, _head_gather_index, _pack_fragments, _weave, p
 from .heads_bf16 import _FusedHeads, _PropHeads, wgrad  # noqa: F401
 from .heads_f32 import (_ColourMLP, _ColourMLPComposed, _ColourMLPGlo, _FieldMLPComposed, _TallLinear,  # noqa: F401
                         tall_linear, tall_matmul)
-from .march_nodes import (GradientScaler, _AffineBlend, _Composite, _CompositeRays, _FieldFeatures, _GradChannel, _tail_fusable,  # noqa: F401
+from .march_nodes import (GradientScaler, _AffineBlend, _Composite, _CompositeRays, _FieldFeatures, _GradChannel, _NegNormalize, _tail_fusable,  # noqa: F401
                           brightness_forward, hash_decay, scale_features)
 from .sky_train import _sky_fusable, sky_forward, sky_forward_fused
 
@@ -73,6 +73,14 @@ def heads_route(mlp, n_features, on_device_f32, autocast_dtype, glo):
     UCN_F32_LIBRARY=1) | "generic" layer by layer.  on_device_f32: features and first weight are float32 device tensors;
     autocast_dtype: torch.get_autocast_dtype("cuda") under autocast, else None; glo: the per-ray GLO modulation or None (a per-ray
     diagonal between bottleneck and colour layers: the routes that fuse or compose the two are out)."""
+    if getattr(mlp, 'enable_pred_normals', False):
+        # the predicted-normal head reads the bottleneck (models.py:570): the one route that materialises it between the density and
+        # the colour layers, in fp32 and under autocast, with and without GLO (DESIGN.md 7h)
+        # (the colour node's own condition below: the reference's topology at a width the fp32 kernels' 16-byte operand loads take)
+        if mlp.disable_rgb or mlp.net_depth_viewdirs != 2 or mlp.skip_layer_dir != 0 or mlp.net_width_viewdirs % 8 != 0:
+            raise NotImplementedError("enable_pred_normals in the training graph needs the reference's colour topology (net_depth_viewdirs = 2, "
+                                      f"skip_layer_dir = 0) at a net_width_viewdirs that is a multiple of 8, got {mlp.net_width_viewdirs}")
+        return "colour_node"
     fused = os.environ.get("UCN_FUSED_HEADS", "1") == "1"
     if glo is None and fused and _heads_shape(mlp, n_features, autocast_dtype):
         return "fused_bf16"
@@ -125,7 +133,7 @@ def _heads_composed_f32(mlp, feat, viewdirs, N, S, chan, glo, one_node=False):
     return F.softplus(raw.reshape(N, S) + mlp.density_bias), rgb_activation(mlp, rgbl.reshape(N, S, -1))
 
 
-def _heads_colour_node(mlp, feat, viewdirs, N, S, chan, glo):
+def _heads_colour_node(mlp, feat, viewdirs, N, S, chan, glo, with_x=False):
     x = tall_linear(mlp.density_layer[2], tall_linear(mlp.density_layer[0], feat, relu=True))    # [N*S, bottleneck]
     enc = view_encoding(viewdirs, mlp.deg_view)                                                  # [N, 27], per ray
     l0, l1 = mlp.lin_second_stage_0, mlp.lin_second_stage_1                                      # the reference's topology
@@ -134,7 +142,8 @@ def _heads_colour_node(mlp, feat, viewdirs, N, S, chan, glo):
     else:
         h, raw = _ColourMLP.apply(x, enc, l0.weight, l0.bias, l1.weight, l1.bias, N, S)
     density = F.softplus(raw.reshape(N, S) + mlp.density_bias)
-    return density, rgb_activation(mlp, tall_linear(mlp.rgb_layer, h).reshape(N, S, -1))
+    rgb = rgb_activation(mlp, tall_linear(mlp.rgb_layer, h).reshape(N, S, -1))
+    return (density, rgb, x) if with_x else (density, rgb)
 
 
 def _heads_generic(mlp, feat, viewdirs, N, S, chan, glo):
@@ -180,6 +189,16 @@ def field_heads(mlp, feat, viewdirs, N, S, chan=None, glo=None):
     return _HEADS[route](mlp, feat, viewdirs, N, S, chan, glo)
 
 
+def field_heads_pred(mlp, feat, viewdirs, N, S, chan=None, glo=None):
+    """`field_heads` of a field with MLP.enable_pred_normals, plus its head (models.py:569-578): (density [N, S], rgb [N, S, 3],
+    grad_pred [N, S, 3] float32).  grad_pred = normal_layer(x) on the bottleneck x the colour node's route materialises (before the GLO
+    modulation), through tall_linear: autograd carries its gradient into normal_layer, the density layers and the tables."""
+    route = heads_route(mlp, feat.shape[1], dense_f32.device_f32(feat, mlp.density_layer[0].weight), _autocast_dtype(), glo)
+    assert route == "colour_node", route
+    density, rgb, x = _heads_colour_node(mlp, feat, viewdirs, N, S, chan, glo, with_x=True)
+    return density, rgb, tall_linear(mlp.normal_layer, x).float().reshape(N, S, 3)
+
+
 def march_train(model, rand, batch, train_frac, compute_extras, eval_camidx, glo_vec=None):
     """Model.forward with an autograd graph (ref models.py:97-365).  glo_vec [N, num_glo_features] (or None): the NeRF level's
     per-ray GLO codes (models.py:118-127); the proposal levels get none (models.py:226)."""
@@ -219,7 +238,12 @@ def march_train(model, rand, batch, train_frac, compute_extras, eval_camidx, glo
         if mlp.scale_featurization:
             feat = torch.cat([feat, scale_features(mlp, posts, rays, flip, spin, S, model.std_scale)], dim=-1)
         glo = None if (is_prop or glo_vec is None) else mlp.glo_affine(glo_vec.reshape(N, -1))
-        density, rgbs = field_heads(mlp, feat, vd, N, S, chan, glo)
+        grad_pred = normals_pred = None
+        if mlp.enable_pred_normals:                                   # models.py:569-578; normals_pred = -l2_normalize(grad_pred)
+            density, rgbs, grad_pred = field_heads_pred(mlp, feat, vd, N, S, chan, glo)
+            normals_pred = _NegNormalize.apply(grad_pred)
+        else:
+            density, rgbs = field_heads(mlp, feat, vd, N, S, chan, glo)
         if getattr(cfg, 'brightness_correction', False):              # models.py:233-235 (gated on this flag)
             rgbs, density = GradientScaler.apply(rgbs, density, tmean)
         bg, ray_bg = ml.background(model, rays, i_level, rand)        # drawn behind the level's MLP (models.py:256)
@@ -250,8 +274,9 @@ def march_train(model, rand, batch, train_frac, compute_extras, eval_camidx, glo
                 raw_grad, normals = torch.empty(N, S, 3, device=dev), torch.empty(N, S, 3, device=dev)
                 ml.density_normals(mlp, posts, rays, flip, spin, slice(None), N, S, model.std_scale, 0, gfeat, raw_grad, normals, st)
         renderings.append(ml.rendering_entry(c_rgb, c_depth, c_acc, weights, extras, prefix, posts.sdist, rgbs, getattr(cfg, 'vis_num_rays', 16),
-                                             normals=normals))
-        hist = ml.history_entry(coord, density, rgbs, posts.sdist, weights, prefix, raw_grad, normals)
+                                             normals=normals, normals_pred=normals_pred))
+        hist = ml.history_entry(coord, density, rgbs, posts.sdist, weights, prefix, raw_grad, normals, grad_pred=grad_pred,
+                                normals_pred=normals_pred)
         if model.training:
             hist['loss_hash_decay'] = hash_decay(mlp)
         ray_history.append(hist)

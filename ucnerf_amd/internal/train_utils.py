@@ -412,6 +412,61 @@ def anti_interlevel_loss(ray_history, config):
     return getattr(config, 'anti_interlevel_loss_mult', 0.01) * total
 
 
+class _Orientation(torch.autograd.Function):
+    """train_utils.py:282-298 for one level, per ray: sum_s w_s max(0, n_s . (-v))^2 as two HIP launches (`ucn_orientation_loss`): forward
+    [N] (summed in double), backward d/dw [N, S] and d/dn [N, S, 3] (every sample its own thread: no atomics).  The view directions
+    carry no gradient."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, w, n, v):
+        lib = _lib.load()
+        w, n, v = w.contiguous(), n.contiguous(), v.contiguous()
+        N, S = w.shape
+        out = torch.empty(N, device=w.device)
+        _lib.check(lib.ucn_orientation_loss(w.data_ptr(), n.data_ptr(), v.data_ptr(), N, S, None, out.data_ptr(), None, _lib.stream()))
+        ctx.save_for_backward(w, n, v)
+        return out
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, g):
+        lib = _lib.load()
+        w, n, v = ctx.saved_tensors
+        N, S = w.shape
+        g = g.reshape(-1).float().contiguous()
+        gw, gn = torch.empty_like(w), torch.empty_like(n)
+        _lib.check(lib.ucn_orientation_loss(w.data_ptr(), n.data_ptr(), v.data_ptr(), N, S, g.data_ptr(), gw.data_ptr(), gn.data_ptr(),
+                                            _lib.stream()))
+        return gw, gn, None
+
+
+def orientation_loss(batch, model, ray_history, config):
+    """ref train_utils.py:282-298 (Ref-NeRF's orientation regulariser): per level mean over rays of sum_s w_s max(0, n_s . (-viewdir))^2
+    on ray_results[config.orientation_loss_target], `orientation_coarse_loss_mult` on the proposal levels and `orientation_loss_mult`
+    on the last.  A level whose target is None raises, whatever the multipliers (as the reference).  Device tensors take the HIP node;
+    the torch form below is the general one."""
+    total_loss = 0.
+    for i, ray_results in enumerate(ray_history):
+        w = ray_results['weights']
+        n = ray_results[config.orientation_loss_target]
+        if n is None:
+            raise ValueError('Normals cannot be None if orientation loss is on.')
+        S = w.shape[-1]
+        v = batch['viewdirs']
+        if _f32_cuda(w, n, v, half_ok=True) and S >= 1 and w.numel() // S == v.numel() // 3 and n.numel() == 3 * w.numel():
+            loss = _Orientation.apply(w.reshape(-1, S), n.reshape(-1, S, 3), v.reshape(-1, 3)).mean()
+        else:
+            # negated viewdirs: unit vectors from the point to the camera
+            n_dot_v = (n * (-1. * v)[..., None, :]).sum(dim=-1)
+            loss = (w * n_dot_v.clamp_min(0) ** 2).sum(dim=-1).mean()
+        if i < model.num_levels - 1:
+            total_loss += config.orientation_coarse_loss_mult * loss
+        else:
+            total_loss += config.orientation_loss_mult * loss
+    return total_loss
+
+
 def distortion_loss(ray_history, config):
     """ref train_utils.py:273-279."""
     last = ray_history[-1]
