@@ -336,6 +336,26 @@ int ucn_points_density_grad(const ucn_field_t *f, const float *means, const floa
 int ucn_pred_normals(const ucn_field_t *f, const float *A, const float *c, const float *features, uint32_t N, uint32_t S, int layout,
                      float *grad_pred_out, float *normals_pred_out, ucn_stream_t stream);
 
+/* ------------------------------------------------- the Ref-NeRF colour heads (added within ABI 32; ref: models.py:447-454, :589-597,
+ * :661-674, MLP.use_diffuse_color / use_specular_tint / enable_pred_roughness; image.py:31-39 linear_to_srgb)
+ * ucn_ref_heads: the heads Linear(bottleneck, 3 | 3 | 1) over x = Wd1 h + bd1 composed as A h + c like ucn_pred_normals, A [R,64] and
+ * c [R] (DEVICE, float32) holding the rows of the heads present in `heads` (bit 0 diffuse, bit 1 tint, bit 2 roughness) in that order.
+ * One call after the level's ucn_field_mlp / ucn_field_rgb_compacted, on the same stream; features and layout as ucn_pred_normals.
+ * With the diffuse bit, rgb [N,S,3] comes in as the colour MLP's sigmoid WITHOUT padding (ucn_field_mlp on a descriptor whose rgb_padding
+ * is 0) and leaves as clip(linear_to_srgb((sigmoid(tint) | 0.5) * rgb + sigmoid(raw_diffuse - ln 3)), 0, 1) * (1 + 2 rgb_padding) -
+ * rgb_padding; without it rgb is not touched (may be NULL) and a tint bit changes nothing.  With the roughness bit and roughness_out
+ * [N,S] non-NULL: softplus(raw + roughness_bias).  Outputs always [ray][s]. */
+int ucn_ref_heads(const ucn_field_t *f, const float *A, const float *c, uint32_t heads, float roughness_bias, float rgb_padding,
+                  const float *features, uint32_t N, uint32_t S, int layout, float *rgb, float *roughness_out, ucn_stream_t stream);
+/* ucn_ref_colour / _backward: the same colour function elementwise over [B,3] from the colour logits (rgb_layer's output), raw_diffuse and
+ * raw_tint (NULL: the factor 0.5): the training graph's node.  The backward gives the three input gradients as torch's autograd of the
+ * reference expression does (the selected srgb part's derivative, the clip passing on 0 <= srgb <= 1).  float32, no atomics. */
+int ucn_ref_colour(const float *logits, const float *raw_diffuse, const float *raw_tint /*|NULL*/, uint64_t B, float rgb_premultiplier,
+                   float rgb_bias, float rgb_padding, float *rgb_out, ucn_stream_t stream);
+int ucn_ref_colour_backward(const float *logits, const float *raw_diffuse, const float *raw_tint /*|NULL*/, const float *g_rgb, uint64_t B,
+                            float rgb_premultiplier, float rgb_bias, float rgb_padding, float *g_logits, float *g_diffuse,
+                            float *g_tint /*|NULL*/, ucn_stream_t stream);
+
 /* ------------------------------------------------- the ray path with the field's warp as an argument (added within ABI 32;
  * ref: MLP.warp_fn, models.py:392 and :488-494; coord.py:93-96 track_linearize knows 'contract' and None)
  * warp = 1: 'contract' -- each call below is then the entry point of the same name without `_warp` (or its `_tdist` sibling), which

@@ -1,0 +1,514 @@
+"""The Ref-NeRF colour heads (MLP.use_diffuse_color, use_specular_tint, enable_pred_roughness) on the device: the colour node and the heads'
+kernel through the C ABI, the inference routes (Model.forward in one and in several passes, MLP.forward, render_image, the compacted march),
+the training graph in fp32 and under bf16 autocast, and a flag-off render that must never reach the new entry points.
+
+Tolerances (the scheme of oracle/truth64.py, tests/test_bracket_gpu.py and tests/test_pred_normals_gpu.py): an error is measured against the
+float64 restatement (tests/ref_colour_ref.py) as max |got - truth| / max |truth| and may reach 4x the float32 reference's own error against
+the same float64 values (ref_colour_ref.allowed); no constant is added.  Quantities computed from the DEVICE's own gather see features that
+differ from the fixture's (the CPU restatement of the grid op) in the last digits, and a level-1 march its own resampled fenceposts: their
+float64 truth is formed from the features and fenceposts the device itself produced (the feature buffer captured at the heads' call), as
+tests/test_pred_normals_gpu.py does; the colour MLP in between -- the existing field kernel -- is inside the bracket.  The allowed error
+stays 4x the float32 reference's own error on the fixture's inputs.  Printed beside it, not asserted: the same colours against the truth that
+also takes the device's own colour-MLP sigmoid as given (the new kernel's share of the error).  Under
+bf16 autocast the gradients are compared to the reference's by cosine >= 0.99 and norm ratio within 5e-2 per tensor: the bars of
+tests/test_train_full_size.py's bf16 case.  The bracket was taken on the fixture's 64-wide layers; the shipped 256-wide ones were not bracketed."""
+import ctypes
+import functools
+import math
+
+import pytest
+import torch
+
+import ref_colour_ref as rc
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+D, T, R = 1, 2, 4
+
+
+@functools.lru_cache(maxsize=None)
+def truth():
+    return rc.restate(torch.float64)
+
+
+@functools.lru_cache(maxsize=None)
+def model_on_device():
+    return rc.build_model(DEV).eval()
+
+
+def t(k):
+    return torch.from_numpy(rc.fixture()[k])
+
+
+def report(name, got, want, ref32=None, bar=None):
+    """got against the float64 `want`; allowed: 4x the error of the float32 reference value `ref32` against it (or the given bar)"""
+    err = rc.rel_err(got, want)
+    bar = rc.allowed(ref32, want) if bar is None else bar
+    print(f"{name}: measured {err:.3e} allowed {bar:.3e}")
+    assert err <= bar, (name, err, bar)
+    return bar
+
+
+def finish(s, raw_diffuse, raw_tint, padding=rc.PADDING):
+    """the colour from the colour MLP's unpadded sigmoid s (what ucn_ref_heads is handed), in the dtype of its arguments"""
+    l = (torch.sigmoid(raw_tint) if raw_tint is not None else 0.5) * s + torch.sigmoid(raw_diffuse - math.log(3.0))
+    return torch.clip(rc.linear_to_srgb(l), 0.0, 1.0) * (1 + 2 * padding) - padding
+
+
+# ---- the colour node through the C ABI ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("tint", [True, False])
+def test_colour_node_on_the_crafted_set(tint):
+    from ucnerf_amd import _lib
+    lib = _lib.load()
+    fx, tag = rc.fixture(), "tint" if tint else "notint"
+    z, rd, rt, G = (t(k).to(DEV).contiguous() for k in ("E_logits", "E_raw_diffuse", "E_raw_tint", "E_G"))
+    kw = rc.head_kw("nerf_mlp")
+    head = (kw["premultiplier"], kw["bias"], rc.PADDING)
+    nan = lambda: torch.full_like(z, float("nan"))
+    out, gz, gd, gt = nan(), nan(), nan(), nan() if tint else None
+    B = z.shape[0]
+    _lib.check(lib.ucn_ref_colour(z.data_ptr(), rd.data_ptr(), rt.data_ptr() if tint else None, B, *head, out.data_ptr(), _lib.stream()))
+    _lib.check(lib.ucn_ref_colour_backward(z.data_ptr(), rd.data_ptr(), rt.data_ptr() if tint else None, G.data_ptr(), B, *head,
+                                           gz.data_ptr(), gd.data_ptr(), _lib.ptr(gt), _lib.stream()))
+    torch.cuda.synchronize()
+    want = rc.crafted(torch.float64, tint)
+    toe, power, clipped, _ = rc.crafted_regimes()[tint]
+    names = ("rgb", "g_logits", "g_raw_diffuse", "g_raw_tint")
+    for regime, m in (("toe", toe), ("power", power), ("clipped", clipped)):
+        assert float(m.double().mean()) >= 0.10
+        for name, got, w64 in zip(names, (out, gz, gd, gt), want):
+            if got is None:
+                continue
+            got, ref32 = got.cpu()[m], torch.from_numpy(fx[f"E_{tag}_{name}"])[m]
+            if name != "rgb" and regime == "clipped":         # the clip passes nothing on: exact zeros, in the reference too
+                assert float(w64[m].abs().max()) == 0.0 and float(ref32.abs().max()) == 0.0
+                assert torch.equal(got, torch.zeros_like(got)), (regime, name)
+                continue
+            report(f"ucn_ref_colour tint={tint} {regime} {name}", got, w64[m], ref32)
+    # the same through the autograd node
+    from ucnerf_amd.internal.march_nodes import _RefColour
+    zz, dd, tt = z.clone().requires_grad_(True), rd.clone().requires_grad_(True), rt.clone().requires_grad_(True)
+    y = _RefColour.apply(zz, dd, tt if tint else None, *head)
+    y.backward(G)
+    assert torch.equal(y.detach(), out) and torch.equal(zz.grad, gz) and torch.equal(dd.grad, gd)
+    assert (tt.grad is None) if not tint else torch.equal(tt.grad, gt)
+    _lib.check(lib.ucn_ref_colour(None, None, None, 0, *head, None, _lib.stream()))          # an empty call launches nothing
+
+
+# ---- the heads' kernel through the C ABI ----------------------------------------------------------------------------------------
+def planes(feat, L, C, layout):
+    """the fixture's [N, S, L*C (+ L)] features as the kernels' [L + scale planes][B][C] buffer, layout 0 (b = ray*S + s) or 2 (b = s*N + ray)"""
+    N, S, F = feat.shape
+    parts = [feat[..., :L * C].reshape(N, S, L, C)]
+    if F > L * C:
+        nsp = (L + C - 1) // C
+        pad = torch.zeros(N, S, nsp * C)
+        pad[..., :L] = feat[..., L * C:]
+        parts.append(pad.reshape(N, S, nsp, C))
+    p = torch.cat(parts, dim=2)
+    p = p.permute(2, 0, 1, 3) if layout == 0 else p.permute(2, 1, 0, 3)
+    return p.contiguous().to(DEV)
+
+
+def head_layers(mask):
+    """the layers of a mask, by name: the proposal field carries the diffuse head only, so every field borrows the NeRF field's tint and
+    roughness layers (all are Linear(64, .) on a 64-wide bottleneck)"""
+    return [n for bit, n in ((D, "diffuse_layer"), (T, "specular_layer"), (R, "roughness_layer")) if mask & bit]
+
+
+@pytest.mark.parametrize("mask", [D, D | T, R, D | T | R])
+@pytest.mark.parametrize("mode", [0, 1])
+@pytest.mark.parametrize("layout", [0, 2])
+def test_heads_kernel_through_the_c_abi(layout, mode, mask):
+    from ucnerf_amd import _lib
+    lib = _lib.load()
+    model, sd = model_on_device(), rc.state()
+    for lvl, (name, mlp) in enumerate(zip(rc.LEVELS, (model.prop_mlp_0, model.nerf_mlp))):
+        feat = t(f"L{lvl}_features")
+        N, S, _ = feat.shape
+        fb = planes(feat, mlp.encoder.num_levels, mlp.encoder.level_dim, layout)
+        own = lambda l: name if f"{name}.{l}.weight" in sd else "nerf_mlp"
+        W = {dt: torch.cat([sd[f"{own(l)}.{l}.weight"].to(dt) for l in head_layers(mask)]) for dt in (torch.float32, torch.float64)}
+        b = {dt: torch.cat([sd[f"{own(l)}.{l}.bias"].to(dt) for l in head_layers(mask)]) for dt in (torch.float32, torch.float64)}
+        d1w, d1b = sd[f"{name}.density_layer.2.weight"].to(DEV), sd[f"{name}.density_layer.2.bias"].to(DEV)
+        A = (W[torch.float32].to(DEV) @ d1w).contiguous()
+        c = (W[torch.float32].to(DEV) @ d1b + b[torch.float32].to(DEV)).contiguous()
+        s_in = truth()[f"L{lvl}_sigmoid"].float()                             # the colour MLP's sigmoid, as the kernel's float32 input
+        rgb = s_in.to(DEV).contiguous() if mask & D else torch.full((N, S, 3), float("nan"), device=DEV)
+        rough = torch.full((N, S), float("nan"), device=DEV)
+        _lib.check(lib.ucn_ref_heads(ctypes.byref(mlp.field(mode)), A.data_ptr(), c.data_ptr(), mask, rc.ROUGHNESS_BIAS, rc.PADDING,
+                                     fb.data_ptr(), N, S, layout, rgb.data_ptr(), rough.data_ptr(), _lib.stream()))
+        torch.cuda.synchronize()
+        want = {}
+        for dt in (torch.float32, torch.float64):                             # the reference's arithmetic in both precisions
+            p = rc.field_params(name, dt, sd)
+            x = rc.lin(p, "density_layer.2", torch.relu(rc.lin(p, "density_layer.0", feat.to(dt))))
+            raw = x @ W[dt].t() + b[dt]
+            col = finish(s_in.to(dt), raw[..., 0:3], raw[..., 3:6] if mask & T else None) if mask & D else None
+            want[dt] = (col, torch.nn.functional.softplus(raw[..., -1] + rc.ROUGHNESS_BIAS) if mask & R else None)
+        tag = f"ucn_ref_heads level {lvl} layout {layout} mode {mode} mask {mask}"
+        if mask & D:
+            report(tag + " rgb", rgb, want[torch.float64][0], want[torch.float32][0])
+        else:
+            assert bool(torch.isnan(rgb).all()), "rgb touched without the diffuse bit"
+        if mask & R:
+            report(tag + " roughness", rough, want[torch.float64][1], want[torch.float32][1])
+        else:
+            assert bool(torch.isnan(rough).all())
+
+
+def test_heads_kernel_edges():
+    """NULL roughness_out with the bit set writes nothing; a tint alone is a no-op; empty and malformed calls"""
+    from ucnerf_amd import _lib
+    lib = _lib.load()
+    mlp = model_on_device().nerf_mlp
+    A, c = mlp.ref_head()
+    assert A.shape == (7, 64) and c.shape == (7,) and mlp.ref_heads_mask() == 7
+    fb = planes(t("L1_features"), 4, 4, 0)
+    N, S = 37, 24
+    rgb = torch.full((N, S, 3), float("nan"), device=DEV)
+    d = mlp.field()
+    call = lambda mask, rgb_p, rough_p, n=N, layout=0: lib.ucn_ref_heads(ctypes.byref(d), A.data_ptr(), c.data_ptr(), mask, -1.0, 0.001,
+                                                                         fb.data_ptr(), n, S, layout, rgb_p, rough_p, _lib.stream())
+    _lib.check(call(R, rgb.data_ptr(), None))
+    _lib.check(call(T, rgb.data_ptr(), None))
+    _lib.check(call(7, None, None, n=0))
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(rgb).all())
+    assert call(0, rgb.data_ptr(), None) != 0 and call(8, rgb.data_ptr(), None) != 0 and call(D, None, None) != 0
+    assert call(D, rgb.data_ptr(), None, layout=1) != 0
+
+
+# ---- the fused march ------------------------------------------------------------------------------------------------------------
+class captured:
+    """While active, every call of march_level.ref_heads also leaves copies of what it read: `.calls` = [(feature buffer, the rays' rgb
+    buffer as handed over, n, S, layout)] in call order."""
+
+    def __enter__(self):
+        from ucnerf_amd.internal import march_level as ml
+        self.ml, self.orig, self.calls = ml, ml.ref_heads, []
+
+        def spy(mlp, desc, head, feat, sl, n, S, layout, rgbs, roughness, stream):
+            self.calls.append((feat.clone(), None if rgbs is None else rgbs[sl].clone(), n, S, layout))
+            return self.orig(mlp, desc, head, feat, sl, n, S, layout, rgbs, roughness, stream)
+        ml.ref_heads = spy
+        return self
+
+    def __exit__(self, *exc):
+        self.ml.ref_heads = self.orig
+        return False
+
+    def features(self, i, mlp):
+        fb, _, n, S, layout = self.calls[i]
+        L, C = mlp.encoder.num_levels, mlp.encoder.level_dim
+        return rc.unplanes(fb.cpu(), L, C, mlp.density_layer[0].in_features, n, S, layout)
+
+
+def own_truth(feats, sigmoids, sdist):
+    """the float64 truth of a march's own features and fenceposts (the restatement on them); under '..._given_sigmoid' the final colour
+    from the device's own colour-MLP sigmoid as well: a diagnostic, the new kernel's share of the error"""
+    own = rc.restate(torch.float64, features=feats, sdist=sdist)
+    for lvl in range(2):
+        own[f"L{lvl}_rgb_given_sigmoid"] = finish(sigmoids[lvl].cpu().double().reshape(own[f"L{lvl}_rgb"].shape), own[f"L{lvl}_raw_diffuse"],
+                                                  own.get(f"L{lvl}_raw_tint"))
+    return own
+
+
+@functools.lru_cache(maxsize=None)
+def marched(chunk=10240, rays_fastest=True, compact=0.0, history=True, extras=True):
+    model = model_on_device()
+    model.max_chunk_rays, model.rays_fastest, model.compact_min_weight = chunk, rays_fastest, compact
+    try:
+        with torch.no_grad(), captured() as cap:
+            if history:
+                rend, hist = model(False, rc.batch(DEV), 1.0, extras)
+            else:
+                rend, hist = model._march(False, rc.batch(DEV), 1.0, extras, None, want_history=False)
+        torch.cuda.synchronize()
+    finally:
+        model.max_chunk_rays, model.rays_fastest, model.compact_min_weight = 10240, True, 0.0
+    own = None
+    if history and chunk >= 37:
+        assert len(cap.calls) == 2
+        feats = [cap.features(i, m) for i, m in enumerate((model.prop_mlp_0, model.nerf_mlp))]
+        own = own_truth(feats, [c[1] for c in cap.calls], [h["sdist"] for h in hist])
+        own["sigmoid_dev"] = [c[1].cpu() for c in cap.calls]
+    return rend, hist, own
+
+
+def test_model_forward_single_and_multi_pass():
+    import helpers as H
+    rend, hist, own = marched()
+    assert model_on_device().last_march_route == "fused"
+    for lvl in range(2):
+        report(f"Model.forward level {lvl} rgb", hist[lvl]["rgb"], own[f"L{lvl}_rgb"], t(f"L{lvl}_rgb"),
+               bar=rc.allowed(t(f"L{lvl}_rgb"), truth()[f"L{lvl}_rgb"]))
+        report(f"Model.forward level {lvl} composited rgb", rend[lvl]["rgb"], own[f"L{lvl}_render_rgb"],
+               bar=rc.allowed(t(f"L{lvl}_render_rgb"), truth()[f"L{lvl}_render_rgb"]))
+        # diagnostics, not asserted: the new kernel alone (the device's sigmoid taken as given), and the field kernel's sigmoid itself
+        e = float((own["sigmoid_dev"][lvl].double().reshape(own[f"L{lvl}_sigmoid"].shape) - own[f"L{lvl}_sigmoid"]).abs().max())
+        print(f"Model.forward level {lvl}: rgb given the device's sigmoid {rc.rel_err(hist[lvl]['rgb'], own[f'L{lvl}_rgb_given_sigmoid']):.3e}; "
+              f"the field MLP's unpadded sigmoid L-inf {e:.3e}")
+        # against the reference's recorded values (its own gather) at the project's fp32 parity bar
+        for got, key in ((hist[lvl]["rgb"], f"L{lvl}_rgb"), (rend[lvl]["rgb"], f"L{lvl}_render_rgb")):
+            e = float((got.cpu() - t(key)).abs().max())
+            print(f"Model.forward {key}: L-inf against the reference {e:.3e} allowed {H.RGB_TOL:.0e}")
+            assert e <= H.RGB_TOL
+    assert hist[0]["roughness"] is None and "roughness" not in rend[0]
+    assert hist[1]["roughness"].shape == (37, 24, 1) and rend[1]["roughness"].shape == (37, 1)
+    report("Model.forward roughness", hist[1]["roughness"], own["L1_roughness"], bar=rc.allowed(t("L1_roughness"), truth()["L1_roughness"]))
+    report("Model.forward composited roughness", rend[1]["roughness"], own["L1_render_roughness"],
+           bar=rc.allowed(t("L1_render_roughness"), truth()["L1_render_roughness"]))
+    # rendering['roughness'] only with compute_extras; the history carries it either way
+    rend0, hist0, _ = marched(extras=False)
+    assert "roughness" not in rend0[1] and torch.equal(hist0[1]["roughness"], hist[1]["roughness"])
+    # 37 rays in passes of 16 and the sample-fastest layout: the same samples through the same arithmetic
+    for kw in (dict(chunk=16), dict(chunk=16, rays_fastest=False), dict(rays_fastest=False)):
+        rend2, hist2, _ = marched(**kw)
+        for lvl in range(2):
+            assert torch.equal(hist2[lvl]["rgb"], hist[lvl]["rgb"]), (kw, lvl)
+            assert torch.equal(rend2[lvl]["rgb"], rend[lvl]["rgb"]), (kw, lvl)
+        assert torch.equal(hist2[1]["roughness"], hist[1]["roughness"]) and torch.equal(rend2[1]["roughness"], rend[1]["roughness"]), kw
+    # an eval-mode call outside no_grad takes the same route
+    model = model_on_device()
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        rend4, hist4 = model(False, rc.batch(DEV), 1.0, True)
+    assert model.last_march_route == "fused" and torch.equal(hist4[1]["rgb"], hist[1]["rgb"])
+
+
+def _marched_compacted(min_weight, chunk):
+    """the last level's rendering of the history-free march (render_image's) with the colour layers compacted, and (alive, total) samples"""
+    model = model_on_device()
+    model.max_chunk_rays, model.compact_min_weight, model._alive_stats = chunk, min_weight, []
+    try:
+        with torch.no_grad():
+            rend, _ = model._march(False, rc.batch(DEV), 1.0, True, None, want_history=False)
+        torch.cuda.synchronize()
+        alive, total = (sum(v) for v in zip(*model._alive_stats))
+    finally:
+        model.max_chunk_rays, model.compact_min_weight, model._alive_stats = 10240, 0.0, None
+    return rend[-1], alive, total
+
+
+@pytest.mark.parametrize("min_weight", [0.035, 0.04])
+def test_compacted_march_stays_within_its_bound(min_weight):
+    """The fixture's NeRF weights start at 0.031: these thresholds kill a part and most of the 888 samples (counted below).  A dead sample's zero-filled
+    rgb leaves ucn_ref_heads as the diffuse-only colour c' <= c (the specular term is non-negative, linear_to_srgb monotone); c <= 1 + padding
+    and c' >= 0 because the fixture's linear diffuse colour stays above 7.8e-5 (asserted), so every dead sample moves the pixel by at most
+    w (1 + padding) < min_weight (1 + padding): the bound S * min_weight * (1 + padding) by construction."""
+    rend, _, _ = marched(history=False)
+    w_ref = truth()["L1_weights"]
+    n_dead_ref = int((w_ref < min_weight).sum())
+    assert float(torch.sigmoid(truth()["L1_raw_diffuse"] - math.log(3.0)).min()) >= 7.8e-5
+    for chunk in (10240, 16):
+        got, alive, total = _marched_compacted(min_weight, chunk)
+        dead = total - alive
+        print(f"compacted march min_weight {min_weight} chunk {chunk}: {dead} of {total} samples dead (float64 truth of the fixture: {n_dead_ref})")
+        assert total == 37 * 24 and 100 <= dead <= total - 100            # samples died, samples lived
+        assert bool(torch.isfinite(got["rgb"]).all()) and bool(torch.isfinite(got["roughness"]).all())
+        bound = 24 * min_weight * (1 + rc.PADDING)
+        err = float((got["rgb"] - rend[-1]["rgb"]).abs().max())
+        print(f"compacted march min_weight {min_weight} chunk {chunk}: |d rgb| {err:.3e} bound {bound:.3e}")
+        assert 0.0 < err <= bound
+        # the roughness pass covers every sample, dead or alive: 8 eps of an O(1) value (the compacted route's weights come from its own
+        # density-only pass)
+        assert float((got["roughness"] - rend[-1]["roughness"]).abs().max()) <= 8 * rc.EPS32
+
+
+def test_render_image_returns_the_roughness():
+    from ucnerf_amd.internal import configs, models
+    model = model_on_device()
+    b = rc.batch(DEV)
+    H, W = 8, 6
+    idx = torch.arange(H * W, device=DEV) % 37                       # pixel i = the fixture's ray i % 37, its cone-basis draws pinned
+    frame = {k: v[idx].reshape(H, W, -1) for k, v in b.items()}
+    out = models.render_image(model, None, frame, False, 1.0, configs.Config(), verbose=False)
+    model.eval()                                                     # (render_image leaves the model in training mode, like the reference)
+    assert out["roughness"].shape == (H, W, 1) and out["rgb"].shape == (H, W, 3)
+    rend, _, _ = marched()
+    for key in ("roughness", "rgb"):
+        got = out[key].reshape(H * W, -1)
+        for lo in (0, 37):
+            part = got[lo:lo + 37]
+            assert float((part - rend[-1][key][:part.shape[0]]).abs().max()) <= 8 * rc.EPS32, key      # 8 eps of an O(1) value
+
+
+def test_mlp_forward():
+    import helpers as H
+    model = model_on_device()
+    vd = t("ray_viewdirs").to(DEV)
+    means, stds, glo = t("F_means").to(DEV), t("F_stds").to(DEV), t("F_glo").to(DEV)
+    sd = rc.state()
+    for name, field_name, mlp, gv in (("prop", "prop_mlp_0", model.prop_mlp_0, None), ("nerf", "nerf_mlp", model.nerf_mlp, None),
+                                      ("nerfglo", "nerf_mlp", model.nerf_mlp, glo)):
+        with captured() as cap:
+            res = mlp(False, means, stds, viewdirs=vd, glo_vec=gv)
+        torch.cuda.synchronize()
+        lvl = rc.LEVELS.index(field_name)
+        assert res["rgb"].shape == (37, 3, 3)
+        assert (res["roughness"] is None) == (name == "prop") and (name == "prop" or res["roughness"].shape == (37, 3, 1))
+        # against the reference's recorded values (its own gather): the project's fp32 parity bar
+        for k, bar in (("rgb", H.RGB_TOL), ("density", H.RGB_TOL), ("roughness", H.RGB_TOL)):
+            if res[k] is None:
+                continue
+            e = float((res[k].cpu() - t(f"F_{name}_{k}")).abs().max())
+            print(f"MLP.forward {name} {k}: L-inf against the reference {e:.3e} allowed {bar:.1e}")
+            assert e <= bar
+        if gv is not None:
+            assert len(cap.calls) == 0                # per-ray codes: the training graph's nodes on the fp32 kernel's bottleneck
+            continue
+        # the fused route: the float64 truth of the features the device gathered; allowed: 4x the reference's own error on the same
+        # field's marched samples (the fixture holds no features of these points)
+        assert len(cap.calls) == 1
+        feat = cap.features(0, mlp).double().reshape(37, 3, -1)
+        p = rc.field_params(field_name, torch.float64, sd)
+        r = rc.field(p, feat, t("ray_viewdirs").double(), None, **rc.head_kw(field_name))
+        given = finish(cap.calls[0][1].cpu().double().reshape(37, 3, 3), r["raw_diffuse"], r["raw_tint"])
+        print(f"MLP.forward {name}: rgb given the device's sigmoid {rc.rel_err(res['rgb'], given):.3e} (diagnostic)")
+        report(f"MLP.forward {name} rgb", res["rgb"], r["rgb"], bar=rc.allowed(t(f"L{lvl}_rgb"), truth()[f"L{lvl}_rgb"]))
+        if r["roughness"] is not None:
+            report(f"MLP.forward {name} roughness", res["roughness"], r["roughness"], bar=rc.allowed(t("L1_roughness"), truth()["L1_roughness"]))
+
+
+# ---- the training graph ---------------------------------------------------------------------------------------------------------
+def _train_step(autocast):
+    from ucnerf_amd.internal import train_graph as tg
+    model = rc.build_model(DEV).train()
+    b = rc.batch(DEV)
+    feats, orig = [], tg.field_heads_ref
+
+    def spy(mlp, feat, viewdirs, N, S, chan=None, glo=None):         # the features the graph's heads read, [N*S, F]
+        feats.append(feat.detach().float().reshape(N, S, -1).cpu())
+        return orig(mlp, feat, viewdirs, N, S, chan, glo)
+    tg.field_heads_ref = spy
+    try:
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=autocast):
+            rend, hist = model(False, b, 1.0, True)
+            loss = sum((rend[lvl]["rgb"].float() * t(f"G{lvl}").to(DEV)).sum() for lvl in range(2))
+    finally:
+        tg.field_heads_ref = orig
+    assert model.last_march_route == "train_graph" and len(feats) == 2
+    loss.backward()
+    torch.cuda.synchronize()
+    grads = {k: (None if p.grad is None else p.grad.detach().cpu()) for k, p in model.named_parameters()}
+    return float(loss.detach()), hist, grads, feats, rend
+
+
+def _roughness_layer_is_untrained(grads):
+    for k in ("nerf_mlp.roughness_layer.weight", "nerf_mlp.roughness_layer.bias"):
+        assert grads[k] is None or float(grads[k].abs().max()) == 0.0, k
+
+
+def test_training_graph_fp32():
+    loss, hist, grads, feats, rend = _train_step(False)
+    own = rc.restate(torch.float64, features=feats, sdist=[h["sdist"] for h in hist])
+    want = float(own["loss"])
+    ref_own = abs(float(t("loss")) - float(truth()["loss"])) / abs(float(truth()["loss"]))
+    # the loss is a signed sum of 2 x 37 x 3 terms: its error is measured against the sum of their magnitudes, like a tensor's against its maximum
+    scale = sum(float((own[f"L{lvl}_render_rgb"] * t(f"G{lvl}").double()).abs().sum()) for lvl in range(2))
+    ref_scaled = abs(float(t("loss")) - float(truth()["loss"])) / sum(float((truth()[f"L{lvl}_render_rgb"] * t(f"G{lvl}").double()).abs().sum())
+                                                                         for lvl in range(2))
+    print(f"loss fp32: got {loss:.8e} truth of the device's features {want:.8e}; measured {abs(loss - want) / scale:.3e} "
+          f"allowed {4 * max(ref_scaled, rc.EPS32):.3e} (relative to the loss itself: {abs(loss - want) / abs(want):.3e}, reference {ref_own:.3e})")
+    assert abs(loss - want) <= 4 * max(ref_scaled, rc.EPS32) * scale
+    for lvl in range(2):
+        for k in ("rgb", "render_rgb"):
+            got = (hist if k == "rgb" else rend)[lvl]["rgb"].detach()
+            report(f"training level {lvl} {k}", got, own[f"L{lvl}_{k}"], bar=rc.allowed(t(f"L{lvl}_{k}"), truth()[f"L{lvl}_{k}"]))
+    report("training roughness", hist[1]["roughness"].detach(), own["L1_roughness"], bar=rc.allowed(t("L1_roughness"), truth()["L1_roughness"]))
+    assert rend[1]["roughness"].shape == (37, 1) and hist[0]["roughness"] is None
+    _roughness_layer_is_untrained(grads)
+    failed = []
+    for key in sorted(k for k in truth() if k.startswith("grad_")):
+        name = key[5:]
+        err, bar = rc.rel_err(grads[name], own[key]), rc.allowed(t(key), truth()[key])
+        print(f"d loss / d {name}: measured {err:.3e} allowed {bar:.3e}")
+        if err > bar:
+            failed.append((name, err, bar))
+    for name in rc.LEVELS:
+        # the table: no float64 restatement of the grid op's backward; the reference's float32 gradient (of ITS features, which differ
+        # from the device's in the last digits), allowed 4x the reference's own error on density_layer.0.weight -- the same upstream
+        # gradients, summed over the samples -- plus the 1e-6 floor tests/test_bracket_gpu.py gives a table gradient
+        k, kw = f"{name}.encoder.embeddings", f"grad_{name}.density_layer.0.weight"
+        err, bar = rc.rel_err(grads[k], t("grad_" + k)), rc.allowed(t(kw), truth()[kw]) + 1e-6
+        print(f"d loss / d {k}: measured {err:.3e} allowed {bar:.3e} (both sides float32)")
+        if err > bar:
+            failed.append((k, err, bar))
+    assert not failed, failed
+
+
+def test_training_graph_bf16():
+    loss, hist, grads, _, _ = _train_step(True)
+    want = float(t("loss"))
+    scale = sum(float((t(f"L{lvl}_render_rgb") * t(f"G{lvl}")).abs().sum()) for lvl in range(2))
+    print(f"loss bf16: got {loss:.6e} reference {want:.6e} (sum of the terms' magnitudes {scale:.4e})")
+    assert abs(loss - want) <= 5e-2 * scale
+    _roughness_layer_is_untrained(grads)
+    failed = []
+    for key in sorted(k for k in rc.fixture() if k.startswith("grad_")):
+        name = key[5:]
+        g, w = grads[name].double().reshape(-1), t(key).double().reshape(-1)
+        if float(w.norm()) == 0.0:                                   # lin_glo_0.weight under the zero code: an exact zero on both sides
+            assert float(g.norm()) == 0.0, name
+            continue
+        cos, ratio = float((g * w).sum() / (g.norm() * w.norm() + 1e-30)), float(g.norm() / w.norm())
+        print(f"bf16 d loss / d {name}: cosine {cos:.5f} norm ratio {ratio:.4f}")
+        if not (cos >= 0.99 and abs(ratio - 1.0) <= 5e-2):
+            failed.append((name, cos, ratio))
+    assert not failed, failed
+
+
+def test_tint_without_the_diffuse_colour_changes_nothing():
+    """models.py:661-668: specular_layer is registered but never read; the colours are the plain field's and the layer gets no gradient"""
+    from ucnerf_amd.internal import configs, models
+    kw = dict(rc.WIDTH, grid_level_dim=2, grid_log2_hashmap_size=8, grid_disired_resolution=64)
+    torch.manual_seed(3)
+    with models.bindings(NerfMLP=dict(kw, use_specular_tint=True), PropMLP=dict(kw, disable_rgb=True)):
+        flagged = models.Model(config=configs.Config(), num_levels=2, num_prop_samples=13, num_nerf_samples=24, prop_desired_grid_size=[64]).to(DEV)
+    with models.bindings(NerfMLP=kw, PropMLP=dict(kw, disable_rgb=True)):
+        plain = models.Model(config=configs.Config(), num_levels=2, num_prop_samples=13, num_nerf_samples=24, prop_desired_grid_size=[64]).to(DEV)
+    plain.load_state_dict({k: v for k, v in flagged.state_dict().items() if "specular_layer" not in k})
+    b = {k: v for k, v in rc.batch(DEV).items() if k != "rand_vec"}
+    torch.manual_seed(5)
+    vec = torch.randn(37, 6, device=DEV)
+    b["rand_vec"] = vec
+    with torch.no_grad():
+        r1, _ = flagged.eval()(False, b, 1.0, True)
+        r0, _ = plain.eval()(False, b, 1.0, True)
+    assert torch.equal(r1[-1]["rgb"], r0[-1]["rgb"]) and "roughness" not in r1[-1]
+    rend, _ = flagged.train()(False, b, 1.0, False)
+    rend[-1]["rgb"].sum().backward()
+    g = flagged.nerf_mlp.specular_layer.weight.grad
+    assert g is None or float(g.abs().max()) == 0.0
+    assert float(flagged.nerf_mlp.rgb_layer.weight.grad.abs().max()) > 0.0
+
+
+def test_flag_off_never_calls_the_entry_points(monkeypatch):
+    from ucnerf_amd import _lib
+    lib = _lib.load()
+    model = rc.build_model(DEV, flag=False).eval()
+    with torch.no_grad():
+        rend0, hist0 = model(False, rc.batch(DEV), 1.0, True)
+    torch.cuda.synchronize()
+    calls = []
+    for name in ("ucn_ref_heads", "ucn_ref_colour", "ucn_ref_colour_backward"):
+        def trap(*a, name=name):
+            calls.append(name)
+            raise AssertionError(f"{name} called for a field without the colour heads")
+        monkeypatch.setattr(lib, name, trap, raising=True)
+    with torch.no_grad():
+        rend, hist = model(False, rc.batch(DEV), 1.0, True)
+    model.train()
+    rend_t, _ = model(False, rc.batch(DEV), 1.0, True)
+    rend_t[-1]["rgb"].sum().backward()
+    torch.cuda.synchronize()
+    assert calls == [] and "roughness" not in rend[-1] and hist[-1]["roughness"] is None and "roughness" not in rend_t[-1]
+    for lvl in range(2):
+        for k in ("rgb", "density", "weights"):
+            assert torch.equal(hist[lvl][k], hist0[lvl][k]), (lvl, k)
+        assert torch.equal(rend[lvl]["rgb"], rend0[lvl]["rgb"])
+    # the same fields' densities are the flagged model's: the heads change the colours only
+    _, hist_on, _ = marched()
+    assert torch.equal(hist[0]["density"], hist_on[0]["density"]) and torch.equal(hist[1]["density"], hist_on[1]["density"])

@@ -116,6 +116,10 @@ SIGNATURES = {
     "ucn_pred_normals": [ctypes.POINTER(UcnField), c_vp, c_vp, c_vp, c_u32, c_u32, c_i32, c_vp, c_vp, c_vp],
     "ucn_neg_normalize": [c_vp, c_u64, c_vp, c_vp, c_vp],
     "ucn_orientation_loss": [c_vp, c_vp, c_vp, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp],
+    # the Ref-NeRF colour heads (MLP.use_diffuse_color / use_specular_tint / enable_pred_roughness; added within ABI 32)
+    "ucn_ref_heads": [ctypes.POINTER(UcnField), c_vp, c_vp, c_u32, c_f32, c_f32, c_vp, c_u32, c_u32, c_i32, c_vp, c_vp, c_vp],
+    "ucn_ref_colour": [c_vp, c_vp, c_vp, c_u64, c_f32, c_f32, c_f32, c_vp, c_vp],
+    "ucn_ref_colour_backward": [c_vp, c_vp, c_vp, c_vp, c_u64, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp],
     "ucn_field_dir_floats": [ctypes.POINTER(UcnField), c_u32],
     "ucn_field_dir_bias": [ctypes.POINTER(UcnField), c_vp, c_u32, c_vp, c_vp],
     "ucn_field_mlp": [ctypes.POINTER(UcnField), c_vp, c_u32, c_u32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp],

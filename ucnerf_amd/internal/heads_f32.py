@@ -77,18 +77,25 @@ class _TallLinear(torch.autograd.Function):
         return gx, gw.to(w_dt), ge, None
 
 
+def tall_affine(x, weight, bias, grad_t=False, relu=False):
+    """x @ weight.T + bias (+ ReLU) through _TallLinear (autocast: operands in bf16 like F.linear under autocast), on the fp32 step through the
+    hand-written fp32 MFMA GEMMs (csrc/gemm_f32.hip), else F.linear: the ONE place that picks among the three.  weight / bias need not be
+    parameters (a stack of several heads' rows).  grad_t, relu: see `tall_linear`."""
+    if torch.is_autocast_enabled():
+        y = _TallLinear.apply(x, weight, bias, grad_t)
+        return F.relu(y) if relu else y
+    if dense_f32.usable(x, weight):               # the fp32 step (train_waymo.sh:3)
+        return dense_f32.hip_linear(x, weight, bias, relu=relu)
+    y = F.linear(x, weight, bias)
+    return F.relu(y) if relu else y
+
+
 def tall_linear(lin, x, grad_t=False, relu=False):
-    """nn.Linear `lin` (+ ReLU) applied through _TallLinear (autocast: operands in bf16 like F.linear under autocast).
+    """nn.Linear `lin` (+ ReLU) applied through `tall_affine`.
     grad_t: the input gradient comes back as the transpose of a contiguous [K, M] matrix (for _FieldFeatures).
     relu: on the fp32 route the ReLU is the GEMM's epilogue (and its output keeps the recorded maximum the next product scales by:
     the waymo.gin proposal level -- 1.9 M rows x 64 -- paid an elementwise pass and an amax pass for a separate F.relu)."""
-    if torch.is_autocast_enabled():
-        y = _TallLinear.apply(x, lin.weight, lin.bias, grad_t)
-        return F.relu(y) if relu else y
-    if dense_f32.usable(x, lin.weight):            # the fp32 step (train_waymo.sh:3): hand-written fp32 MFMA GEMMs (csrc/gemm_f32.hip)
-        return dense_f32.hip_linear(x, lin.weight, lin.bias, relu=relu)
-    y = F.linear(x, lin.weight, lin.bias)
-    return F.relu(y) if relu else y
+    return tall_affine(x, lin.weight, lin.bias, grad_t, relu)
 
 
 def tall_matmul(x, weight, acc=None):

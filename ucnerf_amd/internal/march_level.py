@@ -258,8 +258,20 @@ def pred_normals(desc, head, feat, sl, n, S, layout, grad_pred, normals_pred, st
                                             grad_pred[sl].data_ptr(), normals_pred[sl].data_ptr(), stream))
 
 
+def ref_heads(mlp, desc, head, feat, sl, n, S, layout, rgbs, roughness, stream):
+    """models.py:589-597 and :661-674 for the n rays `sl` of a level, after its dense layers, on `stream`: ucn_ref_heads reads the pass's
+    feature buffer `feat` (as `pred_normals`), turns rgbs[sl] ([N, S, 3], the colour MLP's sigmoid WITHOUT padding) into the final colour in
+    place when the field has the diffuse head, and fills roughness[sl] ([N, S], or None: not wanted).  desc: the level's mlp.field();
+    head: mlp.ref_head().  No autograd graph."""
+    A, c = head
+    _lib.check(_lib.load().ucn_ref_heads(ctypes.byref(desc), A.data_ptr(), c.data_ptr(), mlp.ref_heads_mask(), float(mlp.roughness_bias),
+                                         float(mlp.rgb_padding), feat.data_ptr(), n, S, layout, None if rgbs is None else rgbs[sl].data_ptr(),
+                                         None if roughness is None else roughness[sl].data_ptr(), stream))
+
+
 # ---- result dictionaries (the keys of ref models.py:262-324) -------------------------------------------------------------
-def rendering_entry(rgb, depth, acc, weights, extras, prefix, sdist=None, rgbs=None, n_vis=16, normals=None, normals_pred=None):
+def rendering_entry(rgb, depth, acc, weights, extras, prefix, sdist=None, rgbs=None, n_vis=16, normals=None, normals_pred=None,
+                    roughness=None):
     """rgb [N, 3], depth [N], acc [N], weights [N, S]; with extras [N, 4] (compute_extras: distance mean, 5 %, median, 95 %) also the
     'ray_*' keys: the first n_vis rays' fenceposts, weights and colours (rgbs None, a proposal level: zeros until `broadcast_final`)."""
     N, S = weights.shape
@@ -270,6 +282,9 @@ def rendering_entry(rgb, depth, acc, weights, extras, prefix, sdist=None, rgbs=N
     # training graph too (the reference composites it with the graph attached; no loss reads the rendering: train_utils reads the history)
     if extras is not None and normals_pred is not None:
         r['normals_pred'] = (weights.detach()[..., None] * normals_pred.detach()).sum(dim=-2).reshape(prefix + (3,))
+    # and the roughness [N, S] (models.py:279-283 `k in ['roughness']`), no gradient either: nothing on the path consumes it
+    if extras is not None and roughness is not None:
+        r['roughness'] = (weights.detach() * roughness.detach().reshape(N, S)).sum(dim=-1).reshape(prefix + (1,))
     if extras is not None:
         for j, k in enumerate(('distance_mean', 'distance_percentile_5', 'distance_median', 'distance_percentile_95')):
             r[k] = extras[:, j].reshape(prefix)
@@ -287,13 +302,15 @@ def broadcast_final(renderings):
         r['ray_rgbs'] = final[:, None, :].expand(r['ray_rgbs'].shape)
 
 
-def history_entry(coord, density, rgbs, sdist, weights, prefix, raw_grad=None, normals=None, grad_pred=None, normals_pred=None):
-    """coord [N, S, 3], density [N, S], rgbs [N, S, 3] or None (zeros), sdist [N, S+1], weights [N, S]."""
+def history_entry(coord, density, rgbs, sdist, weights, prefix, raw_grad=None, normals=None, grad_pred=None, normals_pred=None,
+                  roughness=None):
+    """coord [N, S, 3], density [N, S], rgbs [N, S, 3] or None (zeros), sdist [N, S+1], weights [N, S], roughness [N, S] or None."""
     N, S = weights.shape
     rgb = torch.zeros(N, S, 3, device=weights.device) if rgbs is None else rgbs
     return dict(coord=coord.reshape(prefix + (S, 3)), density=density.reshape(prefix + (S,)), rgb=rgb.reshape(prefix + (S, 3)),
                 raw_grad_density=None if raw_grad is None else raw_grad.reshape(prefix + (S, 3)),
                 grad_pred=None if grad_pred is None else grad_pred.reshape(prefix + (S, 3)),
                 normals=None if normals is None else normals.reshape(prefix + (S, 3)),
-                normals_pred=None if normals_pred is None else normals_pred.reshape(prefix + (S, 3)), roughness=None,
+                normals_pred=None if normals_pred is None else normals_pred.reshape(prefix + (S, 3)),
+                roughness=None if roughness is None else roughness.reshape(prefix + (S, 1)),
                 sdist=sdist.reshape(prefix + (S + 1,)).clone(), weights=weights.reshape(prefix + (S,)).clone())

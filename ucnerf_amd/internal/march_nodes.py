@@ -263,6 +263,41 @@ class _NegNormalize(torch.autograd.Function):
         return out
 
 
+class _RefColour(torch.autograd.Function):
+    """models.py:657-674 with use_diffuse_color, in place of `rgb_activation`: the final colour from the colour logits [..., 3], the raw
+    diffuse logits and the raw tint logits (or None: the factor 0.5) as one HIP launch each way (`ucn_ref_colour`, `ucn_ref_colour_backward`;
+    csrc/ref_colour.hip).  float32 inside, whatever the autocast dtype of its inputs."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, logits, raw_diffuse, raw_tint, premultiplier, bias, padding):
+        logits, raw_diffuse = logits.contiguous(), raw_diffuse.contiguous()
+        raw_tint = None if raw_tint is None else raw_tint.contiguous()
+        for name, t in (("logits", logits), ("raw_diffuse", raw_diffuse), ("raw_tint", raw_tint)):
+            if t is not None:
+                _lib.require_device(t, f"_RefColour {name}")
+                if t.shape != logits.shape or t.shape[-1] != 3:
+                    raise RuntimeError(f"_RefColour: {name} {tuple(t.shape)} against logits {tuple(logits.shape)}: expected equal [..., 3] shapes")
+        out = torch.empty_like(logits)
+        ctx.head = (float(premultiplier), float(bias), float(padding))
+        _lib.check(_lib.load().ucn_ref_colour(logits.data_ptr(), raw_diffuse.data_ptr(), _lib.ptr(raw_tint), logits.numel() // 3, *ctx.head,
+                                              out.data_ptr(), _lib.stream()))
+        ctx.save_for_backward(logits, raw_diffuse, raw_tint)
+        return out
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, g):
+        logits, raw_diffuse, raw_tint = ctx.saved_tensors
+        g = g.float().contiguous()
+        g_logits, g_diffuse = torch.empty_like(logits), torch.empty_like(raw_diffuse)
+        g_tint = None if raw_tint is None else torch.empty_like(raw_tint)
+        _lib.check(_lib.load().ucn_ref_colour_backward(logits.data_ptr(), raw_diffuse.data_ptr(), _lib.ptr(raw_tint), g.data_ptr(),
+                                                       logits.numel() // 3, *ctx.head, g_logits.data_ptr(), g_diffuse.data_ptr(),
+                                                       _lib.ptr(g_tint), _lib.stream()))
+        return g_logits, g_diffuse, g_tint, None, None, None
+
+
 class _HashDecay(torch.autograd.Function):
     """models.py:297-306 as one pass over the table forward and one backward (`ucn_hash_decay`); the per-level slices of
     the reference's formulation cost 16 full-table zero-fills and adds in autograd, the torch form of the weighted sum

@@ -9,11 +9,12 @@ signature: a sampling level is five kernel launches on the caller's HIP stream
 composite) instead of ~300 eager ops, and nothing of size [N*S*6, .] is ever materialised.
 
 Supported configuration = the reference's shipped one (configs/waymo.gin): disable_density_normals,
-no reflections / diffuse / IDE, plus GLO appearance codes (num_glo_features > 0; DESIGN.md "GLO") and every
+no reflections / IDE, plus GLO appearance codes (num_glo_features > 0; DESIGN.md "GLO") and every
 ray-distance curve of coord.construct_ray_warps (raydist_fn None, 'piecewise', 'power_transformation' or a gin-bound
 torch.reciprocal / log / exp / sqrt / square; DESIGN.md "Ray-distance curves") and the featurized grid scale
 (MLP.scale_featurization) and analytic density normals (MLP.disable_density_normals = False) and the
-predicted-normal head (MLP.enable_pred_normals).
+predicted-normal head (MLP.enable_pred_normals) and the Ref-NeRF colour heads (MLP.use_diffuse_color, use_specular_tint,
+enable_pred_roughness).
 Anything else raises at construction.
 In eval mode or with gradients disabled forward is the fused inference march; a model in training mode
 with gradients enabled routes to internal/train_graph.py `march_train` (same kernels for resampling and featurisation, HIP
@@ -125,6 +126,7 @@ class MLP(nn.Module):
     rgb_premultiplier: float = 1.
     rgb_bias: float = 0.
     rgb_padding: float = 0.001
+    roughness_bias: float = -1.
     enable_pred_normals: bool = False
     disable_density_normals: bool = True     # waymo.gin:15,17 (upstream class default is False)
     disable_rgb: bool = False
@@ -149,9 +151,20 @@ class MLP(nn.Module):
     def __init__(self, **kwargs):
         super().__init__()
         set_kwargs(self, kwargs)
-        unsupported = dict(use_reflections=False, use_directional_enc=False, enable_pred_roughness=False,
-                           use_diffuse_color=False, use_specular_tint=False, use_n_dot_v=False,
-                           net_depth_viewdirs=2, skip_layer_dir=0, num_rgb_channels=3,
+        # the rest of the reference's Ref-NeRF branch, each refused by name
+        if self.use_reflections or self.use_n_dot_v:
+            k = 'use_reflections' if self.use_reflections else 'use_n_dot_v'
+            raise NotImplementedError(
+                f"{type(self).__name__}.{k}=True: the colour layers would read a per-SAMPLE direction term (the reflected direction's "
+                "encoding, the normal's dot product with the view direction); the fused field kernels take one direction tile per ray. "
+                "Supported of the Ref-NeRF branch: use_diffuse_color, use_specular_tint, enable_pred_roughness, enable_pred_normals "
+                "(DESIGN.md 7i)")
+        if self.use_directional_enc:
+            raise NotImplementedError(
+                f"{type(self).__name__}.use_directional_enc=True: the reference's own forward fails on the integrated directional "
+                "encoding without use_reflections and enable_pred_roughness together (sigma * None, a per-ray against per-sample "
+                "broadcast), and use_reflections is not built (DESIGN.md 7i)")
+        unsupported = dict(net_depth_viewdirs=2, skip_layer_dir=0, num_rgb_channels=3,
                            bottleneck_noise=0.0, density_noise=0.0)
         for k, want in unsupported.items():
             if getattr(self, k) != want:
@@ -195,8 +208,16 @@ class MLP(nn.Module):
             self.normal_layer = nn.Linear(self.bottleneck_width, 3)
         self.dim_dir_enc = 3 + 6 * self.deg_view
         if not self.disable_rgb:
+            # ref models.py:447-454: the Ref-NeRF colour heads, registered here (after normal_layer, before lin_glo_*); with
+            # disable_rgb the flags do nothing, as in the reference
+            if self.use_diffuse_color:
+                self.diffuse_layer = nn.Linear(self.bottleneck_width, self.num_rgb_channels)
+            if self.use_specular_tint:
+                self.specular_layer = nn.Linear(self.bottleneck_width, 3)
+            if self.enable_pred_roughness:
+                self.roughness_layer = nn.Linear(self.bottleneck_width, 1)
             last_dim_rgb = self.bottleneck_width + self.dim_dir_enc
-            if self.num_glo_features > 0:            # ref models.py:467-473: registered before the colour layers
+            if self.num_glo_features > 0:           # ref models.py:467-473: registered before the colour layers
                 last_dim_glo = self.num_glo_features
                 for i in range(self.net_depth_glo - 1):
                     self.register_module(f"lin_glo_{i}", nn.Linear(last_dim_glo, self.net_width_glo))
@@ -213,7 +234,50 @@ class MLP(nn.Module):
             self.rgb_layer = nn.Linear(last_dim_rgb, self.num_rgb_channels)
         self._fields = {}          # (mlp_mode, glo fold) -> (key, ucn_field_t, packed weight stream): one packed buffer each
 
-    _UNPICKLED = ('_fields', '_grid_desc', '_grid_desc_key', '_glo_fold', '_level_scale', '_pred_head')
+    _UNPICKLED = ('_fields', '_grid_desc', '_grid_desc_key', '_glo_fold', '_level_scale', '_pred_head', '_ref_head')
+
+    # ---- the Ref-NeRF colour heads (ref models.py:447-454, :589-597, :661-674) ------------
+    HEAD_DIFFUSE, HEAD_TINT, HEAD_ROUGHNESS = 1, 2, 4            # ucn_ref_heads' mask (include/ucnerf_march.h)
+
+    def ref_heads_mask(self):
+        """The mask of the colour heads this field carries: 0 for a field without them, and with disable_rgb (no layer exists)."""
+        if self.disable_rgb:
+            return 0
+        return ((self.HEAD_DIFFUSE if self.use_diffuse_color else 0) | (self.HEAD_TINT if self.use_specular_tint else 0)
+                | (self.HEAD_ROUGHNESS if self.enable_pred_roughness else 0))
+
+    def ref_head_layers(self):
+        """The present heads' layers in the row order of `ref_head`: diffuse 3, tint 3, roughness 1."""
+        mask = self.ref_heads_mask()
+        return [getattr(self, n) for bit, n in ((self.HEAD_DIFFUSE, 'diffuse_layer'), (self.HEAD_TINT, 'specular_layer'),
+                                                (self.HEAD_ROUGHNESS, 'roughness_layer')) if mask & bit]
+
+    def ref_head(self):
+        """(A = W Wd1 [R, 64], c = W bd1 + b [R]), float32 on the device, W / b the present heads' rows stacked (diffuse 3, tint 3,
+        roughness 1: R <= 7): the heads composed with density_layer.2, what ucn_ref_heads applies to the hidden layer -- the analogue
+        of `pred_head`.  Formed in fp32, recomputed only when one of the parameters changed."""
+        layers, d1 = self.ref_head_layers(), self.density_layer[2]
+        ps = [p for lin in layers for p in (lin.weight, lin.bias)] + [d1.weight, d1.bias]
+        for p in ps:
+            _lib.require_device(p, f"{type(self).__name__} parameter")
+        key = tuple((p.data_ptr(), p._version) for p in ps)
+        hit = getattr(self, '_ref_head', None)
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        with torch.no_grad(), torch.autocast('cuda', enabled=False):
+            W = torch.cat([lin.weight.float() for lin in layers], dim=0)
+            b = torch.cat([lin.bias.float() for lin in layers], dim=0)
+            out = ((W @ d1.weight.float()).contiguous(), (W @ d1.bias.float() + b).contiguous())
+        self._ref_head = (key, out)
+        return out
+
+    def unpadded_field(self, desc):
+        """A copy of the descriptor `desc` whose rgb_padding is 0: ucn_field_mlp then leaves the colour MLP's plain sigmoid
+        (x * 1 - 0, exact), what ucn_ref_heads takes as the linear specular colour.  The caller keeps it alive for its launches."""
+        d = _lib.UcnField()
+        ctypes.memmove(ctypes.byref(d), ctypes.byref(desc), ctypes.sizeof(_lib.UcnField))
+        d.rgb_padding = 0.0
+        return d
 
     # ---- predicted normals (ref models.py:442-444, :569-578; DESIGN.md 7h) -------------------------
     def pred_head(self):
@@ -426,15 +490,16 @@ class MLP(nn.Module):
         node (_ColourMLPGlo) on the fp32 kernel's bottleneck, without gradients."""
         if glo_vec is not None and self.uses_glo() and viewdirs is not None:
             return self._forward_glo(means, stds, viewdirs, glo_vec, no_warp)
-        _, _, coord, density, rgb, (raw_grad, normals, grad_pred, normals_pred) = self._evaluate(means, stds, viewdirs, no_warp, want_x=False)
+        _, _, coord, density, rgb, (raw_grad, normals, grad_pred, normals_pred, roughness) = self._evaluate(means, stds, viewdirs, no_warp,
+                                                                                                           want_x=False)
         if self.disable_rgb or viewdirs is None:
             rgb = torch.zeros(density.shape + (3,), device=density.device)
         return dict(coord=coord, density=density, rgb=rgb, raw_grad_density=raw_grad, grad_pred=grad_pred, normals=normals,
-                    normals_pred=normals_pred, roughness=None)
+                    normals_pred=normals_pred, roughness=roughness)
 
     def _forward_glo(self, means, stds, viewdirs, glo_vec, no_warp):
         from .heads_f32 import _ColourMLPGlo
-        raw, x, coord, _, _, (raw_grad, normals, grad_pred, normals_pred) = self._evaluate(means, stds, None, no_warp, want_x=True)
+        raw, x, coord, _, _, (raw_grad, normals, grad_pred, normals_pred, _) = self._evaluate(means, stds, None, no_warp, want_x=True)
         prefix = raw.shape
         vd = _f32(viewdirs, -1, 3)
         N = vd.shape[0]
@@ -448,9 +513,17 @@ class MLP(nn.Module):
             h, _ = _ColourMLPGlo.apply(x.reshape(B, -1), a, b, view_encoding(vd, self.deg_view), l0.weight, l0.bias,
                                        l1.weight, l1.bias, N, B // N)
             logits = torch.nn.functional.linear(h, self.rgb_layer.weight, self.rgb_layer.bias)
-        rgb = rgb_activation(self, logits)
+        roughness = None
+        if self.ref_heads_mask():
+            # models.py:589-597, :661-674 on the bottleneck before the modulation: the training graph's heads and colour node, without gradients
+            from .train_graph import ref_colour_heads
+            with torch.autocast('cuda', enabled=False):
+                rgb, roughness = ref_colour_heads(self, x.reshape(B, -1), logits)
+            roughness = None if roughness is None else roughness.reshape(prefix + (1,))
+        else:
+            rgb = rgb_activation(self, logits)
         return dict(coord=coord, density=density, rgb=rgb.reshape(prefix + (3,)), raw_grad_density=raw_grad, grad_pred=grad_pred,
-                    normals=normals, normals_pred=normals_pred, roughness=None)
+                    normals=normals, normals_pred=normals_pred, roughness=roughness)
 
     def _evaluate(self, means, stds, viewdirs, no_warp, want_x, want_normals=True):
         # the split-f16 kernel composes the bottleneck away; the API that returns it uses the fp32 kernel's packed copy
@@ -492,8 +565,15 @@ class MLP(nn.Module):
             dirb = torch.empty(lib.ucn_field_dir_floats(ctypes.byref(d), n_rays), device=dev)
             _lib.check(lib.ucn_field_dir_bias(ctypes.byref(d), vd.data_ptr(), n_rays, dirb.data_ptr(), st))
             rgb = torch.empty(B, 3, device=dev)
-        _lib.check(lib.ucn_field_mlp(ctypes.byref(d), feat.data_ptr(), B, spr, 0, _lib.ptr(dirb), density.data_ptr(),
+        ref_mask = self.ref_heads_mask() if rgb is not None else 0           # models.py:587: the heads are evaluated beside the colours only
+        d_mlp = self.unpadded_field(d) if ref_mask & self.HEAD_DIFFUSE else d  # (the diffuse head: the plain sigmoid, finished below)
+        _lib.check(lib.ucn_field_mlp(ctypes.byref(d_mlp), feat.data_ptr(), B, spr, 0, _lib.ptr(dirb), density.data_ptr(),
                                      _lib.ptr(rgb), _lib.ptr(x), st))
+        roughness = None
+        if ref_mask & (self.HEAD_DIFFUSE | self.HEAD_ROUGHNESS):
+            roughness = torch.empty(B, device=dev) if ref_mask & self.HEAD_ROUGHNESS else None
+            ml.ref_heads(self, d, self.ref_head(), feat, slice(None), B, 1, 0, rgb, roughness, st)
+            roughness = None if roughness is None else roughness.reshape(prefix + (1,))
         nrm = (None, None, None, None)
         if want_normals and self.enable_pred_normals:
             # models.py:569-578: the head on the hidden layer, before any GLO modulation; the MLP left the features as they were
@@ -516,7 +596,7 @@ class MLP(nn.Module):
             raw = x[:, 0].reshape(prefix)
             x = x.reshape(prefix + (n_out,))
         return (raw, x, coord.reshape(prefix + (3,)), density.reshape(prefix),
-                None if rgb is None else rgb.reshape(prefix + (3,)), nrm)
+                None if rgb is None else rgb.reshape(prefix + (3,)), nrm + (roughness,))
 
 
 @_configurable
@@ -704,6 +784,8 @@ class Model(nn.Module):
             return None
         if mlp.enable_pred_normals:                # the head's kernel reads the fp32 feature buffer: fp32-class path
             return None
+        if mlp.ref_heads_mask():                   # the same for the Ref-NeRF colour heads
+            return None
         from .train_graph import heads_route
         emb = mlp.encoder.embeddings
         # the level's bf16 kernels are the training step's: the same route decision (no GLO here: every inference march is zero_glo)
@@ -839,6 +921,14 @@ class Model(nn.Module):
             grad_pred = torch.empty(N, S, 3, device=dev) if want_pred else None
             normals_pred = torch.empty(N, S, 3, device=dev) if want_pred else None
             pred_head = mlp.pred_head() if want_pred else None                     # once per level, not per pass
+            # the Ref-NeRF colour heads: the diffuse head changes the colours, so its pass always runs (for every sample,
+            # compacted or not); the roughness only when something returns it.  The dense layers then leave the plain sigmoid
+            ref_mask = mlp.ref_heads_mask()
+            want_rough = bool(ref_mask & mlp.HEAD_ROUGHNESS) and (want_history or compute_extras)
+            want_ref = bool(ref_mask & mlp.HEAD_DIFFUSE) or want_rough
+            roughness = torch.empty(N, S, device=dev) if want_rough else None
+            ref_head = mlp.ref_head() if want_ref else None                        # once per level, not per pass
+            mlp_desc = mlp.unpadded_field(desc) if ref_mask & mlp.HEAD_DIFFUSE else desc
             nc = min(chunk, N)
             feat = torch.empty(planes(mlp) * nc * S * C, device=dev)
             level_scale = mlp.level_scale() if mlp.scale_featurization else None
@@ -851,7 +941,7 @@ class Model(nn.Module):
             overlap = bool(self.overlap_streams) and N > chunk
             co = _lib.LAUNCH_CORESIDENT if (overlap and not is_prop and self.overlap_streams != 2) else 0     # launch shapes that share a CU (2: plain shapes, tails only)
             compact = (not is_prop) and (not want_history) and self.compact_min_weight > 0 and mlp.mlp_mode == 1 and mixed is None
-            run_mlp = self._mlp_route(mlp=mlp, is_prop=is_prop, S=S, desc=desc, mixed=mixed, rays=rays, posts=posts, dirb=level_dirb, co=co,
+            run_mlp = self._mlp_route(mlp=mlp, is_prop=is_prop, S=S, desc=mlp_desc, mixed=mixed, rays=rays, posts=posts, dirb=level_dirb, co=co,
                                       compact=compact, density=density, rgbs=rgbs, weights=weights, main=main, nc=nc)
             feat_desc = ctypes.byref(desc if mixed is None else mixed['desc'])
             feat_layout = ((2 if self.rays_fastest else 0) | co) if mixed is None else (2 | mixed['table_flag'] | (mixed['feat_flag'] if not is_prop else 0))
@@ -895,6 +985,8 @@ class Model(nn.Module):
                 if timed and overlap:
                     m0.record(cur)
                 run_mlp(fb, sl, r0, n)
+                if want_ref:                          # behind the MLP, on its stream, before anything rewrites the pass's feature buffer
+                    ml.ref_heads(mlp, desc, ref_head, fb, sl, n, S, feat_layout & 3, rgbs, roughness, st)
                 if want_normals:                      # behind the MLP, on its stream: the pass's feature buffer becomes gfeat
                     # (with _prof set, e2 below closes after it: the pass's "MLP" time then includes the normals pass)
                     ml.density_normals(mlp, posts, rays, flip, spin, sl, n, S, self.std_scale, feat_layout & 3, fb, raw_grad, normals, st,
@@ -913,10 +1005,11 @@ class Model(nn.Module):
             bg, ray_bg = ml.background(self, rays, i_level, rand)
             ml.composite(posts, density, rgbs, rays.d, gain, ray_bg, bg, self.opaque_background, weights, main, extras, st)
             renderings.append(ml.rendering_entry(main[:, 0:3], main[:, 3], main[:, 4], weights, extras, prefix, posts.sdist, rgbs,
-                                                 getattr(cfg, 'vis_num_rays', 16), normals=normals, normals_pred=normals_pred))
+                                                 getattr(cfg, 'vis_num_rays', 16), normals=normals, normals_pred=normals_pred,
+                                                 roughness=roughness))
             if want_history:
                 ray_history.append(ml.history_entry(coord, density, rgbs, posts.sdist, weights, prefix, raw_grad, normals,
-                                                    grad_pred=grad_pred, normals_pred=normals_pred))
+                                                    grad_pred=grad_pred, normals_pred=normals_pred, roughness=roughness))
 
         if compute_extras:                                             # ref models.py:313-324
             ml.broadcast_final(renderings)

@@ -31,8 +31,8 @@ from .head_pack import (_acc_vec, _head_gather_index, _pack_fragments, _weave, p
                         rgb_activation, view_encoding)
 from .heads_bf16 import _FusedHeads, _PropHeads, wgrad  # noqa: F401
 from .heads_f32 import (_ColourMLP, _ColourMLPComposed, _ColourMLPGlo, _FieldMLPComposed, _TallLinear,  # noqa: F401
-                        tall_linear, tall_matmul)
-from .march_nodes import (GradientScaler, _AffineBlend, _Composite, _CompositeRays, _FieldFeatures, _GradChannel, _NegNormalize, _tail_fusable,  # noqa: F401
+                        tall_affine, tall_linear, tall_matmul)
+from .march_nodes import (GradientScaler, _AffineBlend, _Composite, _CompositeRays, _FieldFeatures, _GradChannel, _NegNormalize, _RefColour, _tail_fusable,  # noqa: F401
                           brightness_forward, hash_decay, scale_features)
 from .sky_train import _sky_fusable, sky_forward, sky_forward_fused
 
@@ -80,6 +80,13 @@ def heads_route(mlp, n_features, on_device_f32, autocast_dtype, glo):
         if mlp.disable_rgb or mlp.net_depth_viewdirs != 2 or mlp.skip_layer_dir != 0 or mlp.net_width_viewdirs % 8 != 0:
             raise NotImplementedError("enable_pred_normals in the training graph needs the reference's colour topology (net_depth_viewdirs = 2, "
                                       f"skip_layer_dir = 0) at a net_width_viewdirs that is a multiple of 8, got {mlp.net_width_viewdirs}")
+        return "colour_node"
+    if getattr(mlp, 'ref_heads_mask', lambda: 0)():
+        # the Ref-NeRF colour heads read the bottleneck too (models.py:589-597): the same route, under the same condition
+        if mlp.net_depth_viewdirs != 2 or mlp.skip_layer_dir != 0 or mlp.net_width_viewdirs % 8 != 0:
+            raise NotImplementedError("use_diffuse_color / use_specular_tint / enable_pred_roughness in the training graph need the reference's "
+                                      "colour topology (net_depth_viewdirs = 2, skip_layer_dir = 0) at a net_width_viewdirs that is a multiple "
+                                      f"of 8, got {mlp.net_width_viewdirs}")
         return "colour_node"
     fused = os.environ.get("UCN_FUSED_HEADS", "1") == "1"
     if glo is None and fused and _heads_shape(mlp, n_features, autocast_dtype):
@@ -133,6 +140,29 @@ def _heads_composed_f32(mlp, feat, viewdirs, N, S, chan, glo, one_node=False):
     return F.softplus(raw.reshape(N, S) + mlp.density_bias), rgb_activation(mlp, rgbl.reshape(N, S, -1))
 
 
+def ref_colour_heads(mlp, x, logits):
+    """models.py:589-597 and :657-674 on the bottleneck x [B, NB] (before the GLO modulation) and the colour logits [B, 3] of a field with
+    Ref-NeRF colour heads: (rgb [B, 3], roughness [B, 1] float32 or None).  The rows of the heads that are READ -- diffuse 3, tint 3 (beside
+    the diffuse colour only: models.py:665), roughness 1 -- go through ONE stacked product on x (autograd's cat splits the weight gradient);
+    the colour is `_RefColour`, the roughness a softplus on its column.  An unread specular_layer gets no gradient, as in the reference."""
+    layers = [mlp.diffuse_layer] if mlp.use_diffuse_color else []
+    if mlp.use_diffuse_color and mlp.use_specular_tint:
+        layers.append(mlp.specular_layer)
+    if mlp.enable_pred_roughness:
+        layers.append(mlp.roughness_layer)
+    raw = None
+    if layers:
+        # (the stack is part of the graph: its backward hands each layer its rows of the weight gradient; R x bottleneck floats per step)
+        W = torch.cat([l.weight for l in layers], dim=0) if len(layers) > 1 else layers[0].weight
+        b = torch.cat([l.bias for l in layers], dim=0) if len(layers) > 1 else layers[0].bias
+        raw = tall_affine(x, W, b).float()
+    roughness = F.softplus(raw[:, -1:] + mlp.roughness_bias) if mlp.enable_pred_roughness else None
+    if not mlp.use_diffuse_color:
+        return rgb_activation(mlp, logits), roughness
+    raw_tint = raw[:, 3:6] if mlp.use_specular_tint else None
+    return _RefColour.apply(logits, raw[:, 0:3], raw_tint, mlp.rgb_premultiplier, mlp.rgb_bias, mlp.rgb_padding), roughness
+
+
 def _heads_colour_node(mlp, feat, viewdirs, N, S, chan, glo, with_x=False):
     x = tall_linear(mlp.density_layer[2], tall_linear(mlp.density_layer[0], feat, relu=True))    # [N*S, bottleneck]
     enc = view_encoding(viewdirs, mlp.deg_view)                                                  # [N, 27], per ray
@@ -142,8 +172,13 @@ def _heads_colour_node(mlp, feat, viewdirs, N, S, chan, glo, with_x=False):
     else:
         h, raw = _ColourMLP.apply(x, enc, l0.weight, l0.bias, l1.weight, l1.bias, N, S)
     density = F.softplus(raw.reshape(N, S) + mlp.density_bias)
-    rgb = rgb_activation(mlp, tall_linear(mlp.rgb_layer, h).reshape(N, S, -1))
-    return (density, rgb, x) if with_x else (density, rgb)
+    roughness = None
+    if getattr(mlp, 'ref_heads_mask', lambda: 0)():
+        rgb, roughness = ref_colour_heads(mlp, x, tall_linear(mlp.rgb_layer, h))
+        rgb = rgb.reshape(N, S, -1)
+    else:
+        rgb = rgb_activation(mlp, tall_linear(mlp.rgb_layer, h).reshape(N, S, -1))
+    return (density, rgb, x, roughness) if with_x else (density, rgb)
 
 
 def _heads_generic(mlp, feat, viewdirs, N, S, chan, glo):
@@ -195,8 +230,19 @@ def field_heads_pred(mlp, feat, viewdirs, N, S, chan=None, glo=None):
     modulation), through tall_linear: autograd carries its gradient into normal_layer, the density layers and the tables."""
     route = heads_route(mlp, feat.shape[1], dense_f32.device_f32(feat, mlp.density_layer[0].weight), _autocast_dtype(), glo)
     assert route == "colour_node", route
-    density, rgb, x = _heads_colour_node(mlp, feat, viewdirs, N, S, chan, glo, with_x=True)
+    density, rgb, x, _ = _heads_colour_node(mlp, feat, viewdirs, N, S, chan, glo, with_x=True)
     return density, rgb, tall_linear(mlp.normal_layer, x).float().reshape(N, S, 3)
+
+
+def field_heads_ref(mlp, feat, viewdirs, N, S, chan=None, glo=None):
+    """`field_heads` of a field with Ref-NeRF colour heads (models.py:589-597, :661-674): (density [N, S], rgb [N, S, 3],
+    grad_pred [N, S, 3] or None, roughness [N, S, 1] or None).  The heads read the bottleneck the colour node's route materialises; with
+    enable_pred_normals the normal head is a product of its own on the same x, as in `field_heads_pred`."""
+    route = heads_route(mlp, feat.shape[1], dense_f32.device_f32(feat, mlp.density_layer[0].weight), _autocast_dtype(), glo)
+    assert route == "colour_node", route
+    density, rgb, x, roughness = _heads_colour_node(mlp, feat, viewdirs, N, S, chan, glo, with_x=True)
+    grad_pred = tall_linear(mlp.normal_layer, x).float().reshape(N, S, 3) if mlp.enable_pred_normals else None
+    return density, rgb, grad_pred, None if roughness is None else roughness.reshape(N, S, 1)
 
 
 def march_train(model, rand, batch, train_frac, compute_extras, eval_camidx, glo_vec=None):
@@ -238,8 +284,11 @@ def march_train(model, rand, batch, train_frac, compute_extras, eval_camidx, glo
         if mlp.scale_featurization:
             feat = torch.cat([feat, scale_features(mlp, posts, rays, flip, spin, S, model.std_scale)], dim=-1)
         glo = None if (is_prop or glo_vec is None) else mlp.glo_affine(glo_vec.reshape(N, -1))
-        grad_pred = normals_pred = None
-        if mlp.enable_pred_normals:                                   # models.py:569-578; normals_pred = -l2_normalize(grad_pred)
+        grad_pred = normals_pred = roughness = None
+        if mlp.ref_heads_mask():                                      # models.py:589-597, :661-674 (and :569-578 beside them)
+            density, rgbs, grad_pred, roughness = field_heads_ref(mlp, feat, vd, N, S, chan, glo)
+            normals_pred = None if grad_pred is None else _NegNormalize.apply(grad_pred)
+        elif mlp.enable_pred_normals:                                   # models.py:569-578; normals_pred = -l2_normalize(grad_pred)
             density, rgbs, grad_pred = field_heads_pred(mlp, feat, vd, N, S, chan, glo)
             normals_pred = _NegNormalize.apply(grad_pred)
         else:
@@ -274,9 +323,9 @@ def march_train(model, rand, batch, train_frac, compute_extras, eval_camidx, glo
                 raw_grad, normals = torch.empty(N, S, 3, device=dev), torch.empty(N, S, 3, device=dev)
                 ml.density_normals(mlp, posts, rays, flip, spin, slice(None), N, S, model.std_scale, 0, gfeat, raw_grad, normals, st)
         renderings.append(ml.rendering_entry(c_rgb, c_depth, c_acc, weights, extras, prefix, posts.sdist, rgbs, getattr(cfg, 'vis_num_rays', 16),
-                                             normals=normals, normals_pred=normals_pred))
+                                             normals=normals, normals_pred=normals_pred, roughness=roughness))
         hist = ml.history_entry(coord, density, rgbs, posts.sdist, weights, prefix, raw_grad, normals, grad_pred=grad_pred,
-                                normals_pred=normals_pred)
+                                normals_pred=normals_pred, roughness=roughness)
         if model.training:
             hist['loss_hash_decay'] = hash_decay(mlp)
         ray_history.append(hist)
