@@ -143,6 +143,49 @@ def allowed(ref32, truth, factor=4.0):
     return factor * max(rel_err(ref32, truth), EPS32)
 
 
+# ---- the corners of the heads' shared kernel body (csrc/hidden_rows.h): g = A relu(W0 f + b0) + c on hand-made inputs -----------------
+HR_L, HR_N, HR_S = 3, 3, 87            # P * C as small as 3 and as odd as 5; B = 261: two workgroups, the second almost empty
+
+
+def hidden_rows_case(C, scale_planes):
+    """Seeded float32 inputs for a field of HR_L levels of width C, with (scale_planes) or without ceil(L / C) scale planes behind them:
+    feat [B, P*C] per sample b, w0 [64, P*C], b0 [64], A [7, 64], c [7], s [N, S, 3] a colour sigmoid.  Some hidden pre-activations are
+    exactly 0 or negative in float32 and in float64 alike: unit 5 is 0 and unit 7 is -0.5 for every sample, unit 9 is 1 * 0.25 - 0.25 on
+    every fifth sample, and every 17th sample has zero features (h = b0, with b0[11] = 0)."""
+    P = HR_L + ((HR_L + C - 1) // C if scale_planes else 0)
+    gen = torch.Generator().manual_seed(100 * C + int(scale_planes))
+    u = lambda *shape: torch.rand(*shape, generator=gen) * 2 - 1
+    feat, w0, b0, A, c = u(HR_N * HR_S, P * C), u(64, P * C), u(64) / 2, u(7, 64) / 4, u(7)
+    w0[5], b0[5] = 0.0, 0.0
+    w0[7], b0[7] = 0.0, -0.5
+    w0[9], b0[9] = 0.0, -0.25
+    w0[9, 0], feat[::5, 0] = 1.0, 0.25
+    feat[3::17], b0[11] = 0.0, 0.0
+    return dict(C=C, P=P, feat=feat, w0=w0, b0=b0, A=A, c=c, s=torch.rand(HR_N, HR_S, 3, generator=gen))
+
+
+def hidden_rows_planes(case, device):
+    """the case's features as the kernels' [P][B][C] buffer"""
+    return case["feat"].reshape(-1, case["P"], case["C"]).permute(1, 0, 2).contiguous().to(device)
+
+
+def hidden_rows_field(case, device):
+    """(a hand-filled ucn_field_t with what the heads' entry points read, the device tensors it points to)"""
+    from ucnerf_amd import _lib
+    w0, b0 = case["w0"].contiguous().to(device), case["b0"].to(device)
+    d = _lib.UcnField()
+    d.w_d0, d.b_d0, d.num_levels, d.level_dim, d.n_scale_planes = w0.data_ptr(), b0.data_ptr(), HR_L, case["C"], case["P"] - HR_L
+    return d, (w0, b0)
+
+
+def hidden_rows_ref(case, dtype, A, c, layout):
+    """A relu(W0 f + b0) + c in `dtype` for the float32 A [R, 64], c [R] the kernel is handed, as [N, S, R]: sample b is ray * S + s
+    (layout 0) or s * N + ray (layout 2)"""
+    feat, w0, b0 = (case[n].to(dtype) for n in ("feat", "w0", "b0"))
+    g = torch.relu(feat @ w0.t() + b0) @ A.to(dtype).t() + c.to(dtype)
+    return g.reshape(HR_N, HR_S, -1) if layout == 0 else g.reshape(HR_S, HR_N, -1).transpose(0, 1)
+
+
 def unplanes(fb, L, C, F, N, S, layout):
     """a kernel feature buffer [L + scale planes][N*S][C] (layout 0: b = ray*S + s, 2: b = s*N + ray) as [N, S, F] features in
     density_layer's column order: L*C grid features, then (F > L*C) the L scale features out of their ceil(L / C) planes"""

@@ -403,6 +403,53 @@ def test_fields_survive_deepcopy_and_pickle():
     assert r.nerf_mlp._fields == {} and torch.equal(r.nerf_mlp.encoder.embeddings, m.nerf_mlp.encoder.embeddings)
 
 
+def test_cached_rebuilds_when_a_parameter_changes_and_copies_drop_the_slots():
+    """models._cached on host tensors: the identical object while no parameter changed; rebuilt after an in-place update (`_version`)
+    and after a parameter is replaced by a new tensor (`data_ptr`); a deepcopy of a field starts with empty slots."""
+    import copy
+    from ucnerf_amd.internal import models
+    mlp = models.NerfMLP(enable_pred_normals=True, use_diffuse_color=True, scale_featurization=True, num_glo_features=4,
+                         bottleneck_width=64, net_width_viewdirs=64, grid_log2_hashmap_size=8, grid_disired_resolution=64)
+    nl, builds = mlp.normal_layer, []
+
+    def build():
+        builds.append(1)
+        return (nl.weight.detach().clone(), nl.bias.detach().clone())
+    get = lambda: models._cached(mlp, "_pred_head", [nl.weight, nl.bias], build)
+    first = get()
+    assert get() is first and len(builds) == 1
+    assert mlp._pred_head[0] == ((nl.weight.data_ptr(), nl.weight._version), (nl.bias.data_ptr(), nl.bias._version))
+    with torch.no_grad():
+        nl.bias.add_(1)
+    second = get()
+    assert second is not first and len(builds) == 2 and torch.equal(second[1], first[1] + 1) and get() is second
+    nl.weight = torch.nn.Parameter(nl.weight.detach().clone())
+    third = get()
+    assert third is not second and len(builds) == 3 and get() is third
+    for slot in ("_ref_head", "_glo_fold", "_level_scale"):
+        models._cached(mlp, slot, [nl.bias], lambda: object())
+    assert all(hasattr(mlp, s) for s in ("_pred_head", "_ref_head", "_glo_fold", "_level_scale"))
+    c = copy.deepcopy(mlp)
+    assert not any(hasattr(c, s) for s in ("_pred_head", "_ref_head", "_glo_fold", "_level_scale")) and c._fields == {}
+    assert torch.equal(c.normal_layer.bias, nl.bias) and hasattr(mlp, "_pred_head")
+
+
+def test_field_copy_changes_only_the_named_members():
+    from ucnerf_amd import _lib
+    from ucnerf_amd.internal import models
+    src = _lib.UcnField()
+    ctypes.memmove(ctypes.byref(src), bytes(range(1, 256)) * 4, ctypes.sizeof(src))           # no member at its default
+    before = bytes(src)
+    d = models._field_copy(src, rgb_padding=0.0, embeddings=0x1234)
+    assert bytes(src) == before and d is not src
+    assert d.rgb_padding == 0.0 and d.embeddings == 0x1234
+    for name, _ in _lib.UcnField._fields_:
+        if name not in ("rgb_padding", "embeddings"):
+            f = getattr(_lib.UcnField, name)
+            assert bytes(d)[f.offset:f.offset + f.size] == before[f.offset:f.offset + f.size], name
+    assert bytes(models._field_copy(src)) == before
+
+
 def test_instance_keeps_its_bound_configuration_after_the_binding_block():
     """A field built under bindings(NerfMLP=dict(bottleneck_width=64, ...)) must describe itself as 64-wide for its
     whole life (the C descriptor is filled from instance attributes per call), not fall back to the restored class

@@ -107,6 +107,35 @@ def test_kernel_clamp_and_empty_call():
     assert lib.ucn_pred_normals(ctypes.byref(d), A.data_ptr(), c.data_ptr(), fb.data_ptr(), 300, 1, 1, g.data_ptr(), n.data_ptr(), _lib.stream()) != 0
 
 
+def hidden_rows_outputs(C, scale_planes, layout):
+    """ucn_pred_normals on pred_normals_ref.hidden_rows_case: (the case, A, c as handed over, grad_pred, normals_pred on the host).  c is
+    moved away from 0 so that no |grad_pred| is small: the unit vectors are then as well conditioned as grad_pred itself."""
+    from ucnerf_amd import _lib
+    case = pr.hidden_rows_case(C, scale_planes)
+    A, c = case["A"][:3].contiguous(), case["c"][:3] + torch.tensor([2.0, -2.0, 2.0])
+    d, keep = pr.hidden_rows_field(case, DEV)
+    fb, Ad, cd = pr.hidden_rows_planes(case, DEV), A.to(DEV), c.to(DEV)
+    g, n = (torch.full((pr.HR_N, pr.HR_S, 3), float("nan"), device=DEV) for _ in range(2))
+    _lib.check(_lib.load().ucn_pred_normals(ctypes.byref(d), Ad.data_ptr(), cd.data_ptr(), fb.data_ptr(), pr.HR_N, pr.HR_S, layout,
+                                            g.data_ptr(), n.data_ptr(), _lib.stream()))
+    torch.cuda.synchronize()
+    return case, A, c, g.cpu(), n.cpu()
+
+
+@pytest.mark.parametrize("layout", [0, 2])
+@pytest.mark.parametrize("scale_planes", [False, True])
+@pytest.mark.parametrize("C", [1, 2, 4, 8])
+def test_shared_body_corners(C, scale_planes, layout):
+    """the kernel body the heads share (csrc/hidden_rows.h) where the fixtures do not reach: every level width, P * C from 3, scale planes
+    in a hand-filled descriptor, a second workgroup that is almost empty, hidden units at exactly 0; bracketed like the tests above"""
+    case, A, c, g, n = hidden_rows_outputs(C, scale_planes, layout)
+    g32, g64 = (pr.hidden_rows_ref(case, dt, A, c, layout) for dt in (torch.float32, torch.float64))
+    for name, got, r32, r64 in (("grad_pred", g, g32, g64), ("normals_pred", n, pr.neg_normalize(g32), pr.neg_normalize(g64))):
+        err, bar = pr.rel_err(got, r64), pr.allowed(r32, r64)
+        print(f"shared body C {C} P {case['P']} layout {layout} {name}: measured {err:.3e} allowed {bar:.3e}")
+        assert err <= bar, (name, err, bar)
+
+
 class captured:
     """While active, every call of march_level.pred_normals (the fused march, MLP.forward) also leaves a copy of the feature buffer it
     read: `.calls` = [(buffer, rays slice, n, S, layout)] in call order."""

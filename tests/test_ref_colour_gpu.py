@@ -179,6 +179,48 @@ def test_heads_kernel_edges():
     assert call(D, rgb.data_ptr(), None, layout=1) != 0
 
 
+def hidden_rows_outputs(C, scale_planes, layout, mask):
+    """ucn_ref_heads on pred_normals_ref.hidden_rows_case: (the case, A, c as handed over -- the mask's rows, packed --, rgb, roughness on
+    the host; rgb starts as the case's sigmoid, roughness as NaN)"""
+    import pred_normals_ref as pr
+    from ucnerf_amd import _lib
+    case = pr.hidden_rows_case(C, scale_planes)
+    rows = [j for bit, js in ((D, (0, 1, 2)), (T, (3, 4, 5)), (R, (6,))) if mask & bit for j in js]
+    A, c = case["A"][rows].contiguous(), case["c"][rows].contiguous()
+    d, keep = pr.hidden_rows_field(case, DEV)
+    fb, Ad, cd = pr.hidden_rows_planes(case, DEV), A.to(DEV), c.to(DEV)
+    rgb, rough = case["s"].to(DEV).contiguous(), torch.full((pr.HR_N, pr.HR_S), float("nan"), device=DEV)
+    _lib.check(_lib.load().ucn_ref_heads(ctypes.byref(d), Ad.data_ptr(), cd.data_ptr(), mask, rc.ROUGHNESS_BIAS, rc.PADDING, fb.data_ptr(),
+                                         pr.HR_N, pr.HR_S, layout, rgb.data_ptr(), rough.data_ptr(), _lib.stream()))
+    torch.cuda.synchronize()
+    return case, A, c, rgb.cpu(), rough.cpu()
+
+
+@pytest.mark.parametrize("mask", range(1, 8))
+@pytest.mark.parametrize("layout", [0, 2])
+@pytest.mark.parametrize("scale_planes", [False, True])
+@pytest.mark.parametrize("C", [1, 2, 4, 8])
+def test_shared_body_corners(C, scale_planes, layout, mask):
+    """the sibling of tests/test_pred_normals_gpu.py's test of the same name, for every mask: the seven zero-padded rows behind the shared
+    kernel body (csrc/hidden_rows.h).  A buffer whose head is absent, or (the tint) never read, keeps its bits."""
+    import pred_normals_ref as pr
+    case, A, c, rgb, rough = hidden_rows_outputs(C, scale_planes, layout, mask)
+    want = {}
+    for dt in (torch.float32, torch.float64):
+        raw = pr.hidden_rows_ref(case, dt, A, c, layout)
+        col = finish(case["s"].to(dt), raw[..., 0:3], raw[..., 3:6] if mask & T else None) if mask & D else None
+        want[dt] = (col, torch.nn.functional.softplus(raw[..., -1] + rc.ROUGHNESS_BIAS) if mask & R else None)
+    tag = f"shared body C {C} P {case['P']} layout {layout} mask {mask}"
+    if mask & D:
+        report(tag + " rgb", rgb, want[torch.float64][0], want[torch.float32][0])
+    else:
+        assert torch.equal(rgb, case["s"]), "rgb touched without the diffuse bit"
+    if mask & R:
+        report(tag + " roughness", rough, want[torch.float64][1], want[torch.float32][1])
+    else:
+        assert bool(torch.isnan(rough).all())
+
+
 # ---- the fused march ------------------------------------------------------------------------------------------------------------
 class captured:
     """While active, every call of march_level.ref_heads also leaves copies of what it read: `.calls` = [(feature buffer, the rays' rgb

@@ -24,13 +24,9 @@
 #include "ucn_common.h"
 #include "grid_cast.h"
 #include "grid_rows.h"
+#include "hidden_rows.h"      // kHidden, density_layer.0's width; k_density_feature_grad keeps all 64 units live for its backward
 
 namespace {
-
-// density_layer.0's width (models.py:438-441).  Nothing in ucn_field_t carries it: the host builds density_layer as 64 -> 1 + bottleneck
-// for every field (internal/models.py), w_d0 is read as [64][L*C] and row 0 of w_d1 as 64 floats; a field of another width needs
-// the width in the ABI first.
-constexpr uint32_t kHidden = 64;
 
 // features / gfeat: [L][B][C]; they may be the SAME buffer (a thread reads its sample's features before it writes them)
 template <uint32_t C>

@@ -6,15 +6,13 @@
 //     rgb = clip(linear_to_srgb(l), 0, 1) * (1 + 2 padding) - padding
 //     linear_to_srgb(l) = 323/25 l  where l <= 0.0031308,  (211 max(l, float32 eps)^(5/12) - 11) / 200  otherwise      (image.py:31-39)
 //
-// ucn_ref_heads is the inference pass: as ucn_pred_normals (pred_normals.hip) the heads compose with density_layer.2 into A h + c on the
-// hidden layer h = relu(W0 feat + b0), recomputed in plain fp32 from the UNPACKED density_layer.0 in every mlp_mode, weights in LDS (every
-// lane reads the same word: a broadcast), one sample per thread, the hidden units 16 at a time.  ucn_ref_colour / _backward are the training
-// graph's elementwise node.  All arithmetic float32, powf / expf / log1pf the accurate library functions; no atomics, no workspace.
-#include "ucn_common.h"
+// ucn_ref_heads is the inference pass: the heads compose with density_layer.2 into A h + c on the hidden layer h = relu(W0 feat + b0),
+// whose recompute and the seven rows are hidden_rows.h's.  ucn_ref_colour / _backward are the training graph's elementwise node.
+// All arithmetic float32, powf / expf / log1pf the accurate library functions; no atomics, no workspace.
+#include "hidden_rows.h"
 
 namespace {
 
-constexpr uint32_t kHidden = 64;      // density_layer.0's width (models.py:438-441); see march_normals.hip: nothing in ucn_field_t carries it
 constexpr uint32_t kRows = 7;         // diffuse 3, tint 3, roughness 1: the rows of A in LDS (absent heads: zero rows)
 constexpr float kLn3 = 1.09861228866810969f;
 constexpr float kToe = 0.0031308f;
@@ -52,13 +50,10 @@ __global__ __launch_bounds__(256) void k_ref_heads(const float *__restrict__ w0,
                                                    const float *__restrict__ cvec, uint32_t P, uint32_t heads, float roughness_bias,
                                                    float padding, const float *__restrict__ features, uint32_t N, uint32_t S, int layout,
                                                    float *__restrict__ rgb, float *__restrict__ roughness_out) {
-    extern __shared__ float s_w[];                                  // [64][F] W0, then b0 [64], A [7][64], c [7]
-    const uint32_t F = P * C;
-    float *s_b = s_w + kHidden * F, *s_a = s_b + kHidden, *s_c = s_a + kRows * kHidden;
+    const HiddenLds lds = stage_hidden(w0, b0, P * C);              // then A [7][64], c [7]
+    float *s_a = lds.rest, *s_c = s_a + kRows * kHidden;
     const bool has_d = heads & 1u, has_t = (heads & 2u) && has_d, has_r = heads & 4u;      // the tint is read only beside the diffuse colour
     const uint32_t row_t = has_d ? 3u : 0u, row_r = row_t + ((heads & 2u) ? 3u : 0u);       // rows of A as the caller packed them
-    for (uint32_t i = threadIdx.x; i < kHidden * F; i += 256u) s_w[i] = w0[i];
-    if (threadIdx.x < kHidden) s_b[threadIdx.x] = b0[threadIdx.x];
     for (uint32_t i = threadIdx.x; i < kRows * kHidden; i += 256u) {
         const uint32_t j = i / kHidden, k = i - j * kHidden;
         float v = 0.0f;
@@ -79,40 +74,9 @@ __global__ __launch_bounds__(256) void k_ref_heads(const float *__restrict__ w0,
     const size_t B = (size_t)N * S;
     const size_t b = (size_t)blockIdx.x * 256u + threadIdx.x;
     if (b >= B) return;
-    // the hidden units in chunks of kChunk, as k_pred_normals: all 64 in one plane loop took 256 VGPRs there
-    constexpr uint32_t kChunk = 16;
     float g[kRows];
-#pragma unroll
-    for (uint32_t j = 0; j < kRows; j++) g[j] = s_c[j];
-#pragma unroll 1
-    for (uint32_t k0 = 0; k0 < kHidden; k0 += kChunk) {
-        float h[kChunk];
-#pragma unroll
-        for (uint32_t k = 0; k < kChunk; k++) h[k] = s_b[k0 + k];
-        const float *wk = s_w + k0 * F;
-#pragma unroll 1
-        for (uint32_t p = 0; p < P; p++) {
-            float f[C];
-            const float *fp = features + ((size_t)p * B + b) * C;
-#pragma unroll
-            for (uint32_t c = 0; c < C; c++) f[c] = fp[c];
-#pragma unroll
-            for (uint32_t k = 0; k < kChunk; k++)
-#pragma unroll
-                for (uint32_t c = 0; c < C; c++) h[k] = fmaf(wk[k * F + p * C + c], f[c], h[k]);
-        }
-#pragma unroll
-        for (uint32_t k = 0; k < kChunk; k++) {
-            const float r = fmaxf(h[k], 0.0f);
-#pragma unroll
-            for (uint32_t j = 0; j < kRows; j++) g[j] = fmaf(s_a[j * kHidden + k0 + k], r, g[j]);
-        }
-    }
-    size_t o = b;
-    if (layout == 2) {
-        const uint32_t s = (uint32_t)(b / N), ray = (uint32_t)(b - (size_t)s * N);
-        o = (size_t)ray * S + s;
-    }
+    hidden_rows<C>(lds, s_a, s_c, P, features, B, b, g);
+    const size_t o = ray_major_index(b, N, S, layout);
     if (has_d) {
 #pragma unroll
         for (uint32_t k = 0; k < 3; k++) {
@@ -158,21 +122,14 @@ __global__ __launch_bounds__(256) void k_ref_colour_bwd(const float *__restrict_
 extern "C" int ucn_ref_heads(const ucn_field_t *f, const float *A, const float *c, uint32_t heads, float roughness_bias, float rgb_padding,
                              const float *features, uint32_t N, uint32_t S, int layout, float *rgb, float *roughness_out,
                              ucn_stream_t stream) {
-    UCN_REQUIRE(f && f->w_d0 && f->b_d0, "ref_heads: the field's density_layer.0 pointers are missing");
-    UCN_REQUIRE(f->num_levels >= 1 && f->num_levels <= UCN_MAX_LEVELS, "ref_heads: num_levels must be in [1,%d], got %u", UCN_MAX_LEVELS,
-                f->num_levels);
-    const uint32_t C = f->level_dim, P = f->num_levels + f->n_scale_planes;
-    UCN_REQUIRE(C == 1 || C == 2 || C == 4 || C == 8, "GridEncoding: C must be 1, 2, 4, or 8.");
-    UCN_REQUIRE(layout == 0 || layout == 2, "ref_heads: layout must be 0 or 2");
+    uint32_t P, C;
+    size_t B, lds;
+    if (int e = hidden_rows_args("ref_heads", f, layout, N, S, kRows * kHidden + 8u, &P, &C, &B, &lds)) return e;
     UCN_REQUIRE(heads >= 1 && heads <= 7, "ref_heads: heads must be a mask of 1 (diffuse), 2 (tint), 4 (roughness), got %u", heads);
-    if (N == 0 || S == 0) return 0;
+    if (B == 0) return 0;
     UCN_REQUIRE(A && c && features, "ref_heads: null pointer argument");
     UCN_REQUIRE(!(heads & 1u) || rgb, "ref_heads: the diffuse head needs the rgb buffer");
     if (!(heads & 1u) && !((heads & 4u) && roughness_out)) return 0;         // a tint without the diffuse colour is never read (models.py:661-668)
-    const size_t B = (size_t)N * S;
-    UCN_REQUIRE(B <= 0xFFFFFF00ull, "ref_heads: too many samples in one call (%zu)", B);
-    const size_t lds = ((size_t)kHidden * P * C + kHidden + kRows * kHidden + 8u) * sizeof(float);
-    UCN_REQUIRE(lds <= 64u * 1024u, "ref_heads: %u features do not fit the weight tile", P * C);
     ucn_for_level_dim(C, [&](auto cc) {
         hipLaunchKernelGGL(k_ref_heads<decltype(cc)::value>, dim3(ucn_div_up(B, 256)), dim3(256), lds, (hipStream_t)stream, f->w_d0, f->b_d0,
                            A, c, P, heads, roughness_bias, rgb_padding, features, N, S, layout, rgb, roughness_out);

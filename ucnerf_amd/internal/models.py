@@ -74,6 +74,35 @@ def glo_fold(W0, b0, W1, b1, a, b):
     return W0f, b0 + W0x @ b, W1f, b1 + W1x @ b
 
 
+def _cached(obj, slot, params, build):
+    """build()'s value, kept on `obj` as `slot` = (key, value) and rebuilt only when one of `params` was updated in place or
+    replaced: key = their (data_ptr, _version)."""
+    key = tuple((p.data_ptr(), p._version) for p in params)
+    hit = getattr(obj, slot, None)
+    if hit is None or hit[0] != key:
+        hit = (key, build())
+        setattr(obj, slot, hit)
+    return hit[1]
+
+
+def _require_f32(params, what):
+    """every parameter on the device (`what`: how the message names them), contiguous float32: the kernels read them through raw pointers"""
+    for p in params:
+        _lib.require_device(p, what)
+        if p.dtype != torch.float32 or not p.is_contiguous():
+            raise RuntimeError("field parameters must be contiguous float32")
+
+
+def _field_copy(desc, **members):
+    """A copy of the descriptor `desc` with the named members overridden.  The caller keeps it, and what its pointers name, alive for
+    the launches it makes with it."""
+    d = _lib.UcnField()
+    ctypes.memmove(ctypes.byref(d), ctypes.byref(desc), ctypes.sizeof(_lib.UcnField))
+    for k, v in members.items():
+        setattr(d, k, v)
+    return d
+
+
 # Model.raydist_fn -> the curve id of include/ucnerf_march.h (UCN_RAYDIST_*).  coord.py:151-172 selects a callable by its
 # __name__ and inverts it through `inv_mapping`; the gin-bound callables are configs.py:13-19's torch functions.
 RAYDIST_CURVES = {None: 0, 'piecewise': 1, 'power_transformation': 2}
@@ -254,49 +283,35 @@ class MLP(nn.Module):
 
     def ref_head(self):
         """(A = W Wd1 [R, 64], c = W bd1 + b [R]), float32 on the device, W / b the present heads' rows stacked (diffuse 3, tint 3,
-        roughness 1: R <= 7): the heads composed with density_layer.2, what ucn_ref_heads applies to the hidden layer -- the analogue
-        of `pred_head`.  Formed in fp32, recomputed only when one of the parameters changed."""
-        layers, d1 = self.ref_head_layers(), self.density_layer[2]
+        roughness 1: R <= 7): the heads composed with density_layer.2, what ucn_ref_heads applies to the hidden layer."""
+        return self._hidden_head('_ref_head', self.ref_head_layers())
+
+    def _hidden_head(self, slot, layers):
+        """(A = W Wd1 [R, 64], c = W bd1 + b [R]), float32 on the device, W / b the `layers`' rows stacked: Linear(bottleneck, .) heads
+        composed with density_layer.2 (the inference kernels never materialise the bottleneck).  Two small fp32 products, recomputed
+        only when one of the parameters changed."""
+        d1 = self.density_layer[2]
         ps = [p for lin in layers for p in (lin.weight, lin.bias)] + [d1.weight, d1.bias]
         for p in ps:
             _lib.require_device(p, f"{type(self).__name__} parameter")
-        key = tuple((p.data_ptr(), p._version) for p in ps)
-        hit = getattr(self, '_ref_head', None)
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        with torch.no_grad(), torch.autocast('cuda', enabled=False):
-            W = torch.cat([lin.weight.float() for lin in layers], dim=0)
-            b = torch.cat([lin.bias.float() for lin in layers], dim=0)
-            out = ((W @ d1.weight.float()).contiguous(), (W @ d1.bias.float() + b).contiguous())
-        self._ref_head = (key, out)
-        return out
+
+        def compose():
+            with torch.no_grad(), torch.autocast('cuda', enabled=False):
+                W = torch.cat([lin.weight.float() for lin in layers], dim=0)
+                b = torch.cat([lin.bias.float() for lin in layers], dim=0)
+                return (W @ d1.weight.float()).contiguous(), (W @ d1.bias.float() + b).contiguous()
+        return _cached(self, slot, ps, compose)
 
     def unpadded_field(self, desc):
         """A copy of the descriptor `desc` whose rgb_padding is 0: ucn_field_mlp then leaves the colour MLP's plain sigmoid
         (x * 1 - 0, exact), what ucn_ref_heads takes as the linear specular colour.  The caller keeps it alive for its launches."""
-        d = _lib.UcnField()
-        ctypes.memmove(ctypes.byref(d), ctypes.byref(desc), ctypes.sizeof(_lib.UcnField))
-        d.rgb_padding = 0.0
-        return d
+        return _field_copy(desc, rgb_padding=0.0)
 
     # ---- predicted normals (ref models.py:442-444, :569-578; DESIGN.md 7h) -------------------------
     def pred_head(self):
         """(A = Wn Wd1 [3, 64], c = Wn bd1 + bn [3]), float32 on the device: normal_layer composed with density_layer.2, what
-        ucn_pred_normals applies to the hidden layer (the inference kernels never materialise the bottleneck).  Two small fp32
-        products, recomputed only when one of the four parameters changed."""
-        nl, d1 = self.normal_layer, self.density_layer[2]
-        ps = [nl.weight, nl.bias, d1.weight, d1.bias]
-        for p in ps:
-            _lib.require_device(p, f"{type(self).__name__} parameter")
-        key = tuple((p.data_ptr(), p._version) for p in ps)
-        hit = getattr(self, '_pred_head', None)
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        with torch.no_grad(), torch.autocast('cuda', enabled=False):
-            Wn = nl.weight.float()
-            out = ((Wn @ d1.weight.float()).contiguous(), (Wn @ d1.bias.float() + nl.bias.float()).contiguous())
-        self._pred_head = (key, out)
-        return out
+        ucn_pred_normals applies to the hidden layer."""
+        return self._hidden_head('_pred_head', [self.normal_layer])
 
     # ---- scale featurization (ref models.py:436-437, :497-506; DESIGN.md 7c) ---------------------
     def scale_planes(self):
@@ -310,19 +325,15 @@ class MLP(nn.Module):
         """k [L] on the device: sqrt(init_std^2 + per-level mean of sum_c embeddings^2) of the fp32 table (models.py:498-505, no
         gradient), by ucn_level_scale.  Recomputed only when the table changed: once per render, once per training step."""
         emb, enc = self.encoder.embeddings, self.encoder
-        _lib.require_device(emb, f"{type(self).__name__}.encoder.embeddings")
-        if emb.dtype != torch.float32 or not emb.is_contiguous():
-            raise RuntimeError("field parameters must be contiguous float32")
-        key = (emb.data_ptr(), emb._version)
-        hit = getattr(self, '_level_scale', None)
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        out = torch.empty(enc.num_levels, device=emb.device)
-        ws = torch.empty(_lib.LEVEL_SCALE_WS_FLOATS, device=emb.device)
-        _lib.check(_lib.load().ucn_level_scale(emb.data_ptr(), enc._offsets_np.ctypes.data, enc.num_levels, enc.level_dim,
-                                               float(enc.init_std), out.data_ptr(), ws.data_ptr(), _lib.stream()))
-        self._level_scale = (key, out)
-        return out
+        _require_f32([emb], f"{type(self).__name__}.encoder.embeddings")
+
+        def launch():
+            out = torch.empty(enc.num_levels, device=emb.device)
+            ws = torch.empty(_lib.LEVEL_SCALE_WS_FLOATS, device=emb.device)
+            _lib.check(_lib.load().ucn_level_scale(emb.data_ptr(), enc._offsets_np.ctypes.data, enc.num_levels, enc.level_dim,
+                                                   float(enc.init_std), out.data_ptr(), ws.data_ptr(), _lib.stream()))
+            return out
+        return _cached(self, '_level_scale', [emb], launch)
 
     # ---- GLO appearance codes (ref models.py:600-614) ---------------------------------------------
     def uses_glo(self):
@@ -349,16 +360,13 @@ class MLP(nn.Module):
         inference kernels run when every ray's code is zero (zero_glo=True).  Recomputed only when a parameter changed."""
         l0, l1 = self.lin_second_stage_0, self.lin_second_stage_1
         ps = [l0.weight, l0.bias, l1.weight, l1.bias] + [p for lin in self._glo_layers() for p in (lin.weight, lin.bias)]
-        key = tuple((p.data_ptr(), p._version) for p in ps)
-        hit = getattr(self, '_glo_fold', None)
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        with torch.no_grad(), torch.autocast('cuda', enabled=False):
-            z = torch.zeros(1, self.num_glo_features, device=l0.weight.device)
-            a, b = self.glo_affine(z)
-            out = tuple(t.contiguous() for t in glo_fold(l0.weight, l0.bias, l1.weight, l1.bias, a[0], b[0]))
-        self._glo_fold = (key, out)
-        return out
+
+        def fold():
+            with torch.no_grad(), torch.autocast('cuda', enabled=False):
+                z = torch.zeros(1, self.num_glo_features, device=l0.weight.device)
+                a, b = self.glo_affine(z)
+                return tuple(t.contiguous() for t in glo_fold(l0.weight, l0.bias, l1.weight, l1.bias, a[0], b[0]))
+        return _cached(self, '_glo_fold', ps, fold)          # (_glo_fold[0], the key, is part of `field`'s)
 
     def __getstate__(self):
         """copy.deepcopy / torch.save(model): the cached C descriptors hold raw device pointers (ctypes objects with
@@ -387,10 +395,7 @@ class MLP(nn.Module):
         mode = int(self.mlp_mode if mode is None else mode)
         glo_fold = bool(glo_fold) and self.uses_glo()
         ws = self._weights(glo_fold)
-        for w in ws:
-            _lib.require_device(w, f"{type(self).__name__} parameter")
-            if w.dtype != torch.float32 or not w.is_contiguous():
-                raise RuntimeError("field parameters must be contiguous float32")
+        _require_f32(ws, f"{type(self).__name__} parameter")
         key = tuple((w.data_ptr(), w._version) for w in ws)
         if glo_fold:
             key += self._glo_fold[0]             # the folded copies are new tensors: their source parameters decide
@@ -401,11 +406,7 @@ class MLP(nn.Module):
         lib = _lib.load()
         enc = self.encoder
         d = _lib.UcnField()
-        d.embeddings = ws[0].data_ptr()
-        d.offsets_host = enc._offsets_np.ctypes.data
-        d.grid_sizes_host = enc._sizes_np.ctypes.data
-        d.num_levels, d.level_dim, d.base_resolution = enc.num_levels, enc.level_dim, enc.base_resolution
-        d.log2_per_level_scale = float(np.log2(enc.per_level_scale))
+        self._fill_grid(d, ws[0].data_ptr())
         d.w_d0, d.b_d0, d.w_d1, d.b_d1 = (w.data_ptr() for w in ws[1:5])
         d.n_bottleneck = 1 if self.disable_rgb else self.bottleneck_width
         if not self.disable_rgb:
@@ -435,6 +436,15 @@ class MLP(nn.Module):
         self._fields[mode_key] = (key, d, packed, w_d0)        # (w_d0: kept alive for mode 0, whose kernels are not its only readers)
         return d
 
+    def _fill_grid(self, d, emb_ptr):
+        """the hash-grid members of the descriptor `d`, reading the table at `emb_ptr`"""
+        enc = self.encoder
+        d.embeddings = emb_ptr
+        d.offsets_host = enc._offsets_np.ctypes.data
+        d.grid_sizes_host = enc._sizes_np.ctypes.data
+        d.num_levels, d.level_dim, d.base_resolution = enc.num_levels, enc.level_dim, enc.base_resolution
+        d.log2_per_level_scale = float(np.log2(enc.per_level_scale))
+
     def grid_field(self):
         """ucn_field_t with only the hash-grid part filled in: all the featurisation kernels read.  The training graph
         uses it so that an optimiser step does not trigger a re-pack of the RENDERING engine's weight stream."""
@@ -442,13 +452,8 @@ class MLP(nn.Module):
         _lib.require_device(emb, f"{type(self).__name__}.encoder.embeddings")
         key = (emb.data_ptr(),)
         if getattr(self, "_grid_desc_key", None) != key:
-            enc = self.encoder
             d = _lib.UcnField()
-            d.embeddings = emb.data_ptr()
-            d.offsets_host = enc._offsets_np.ctypes.data
-            d.grid_sizes_host = enc._sizes_np.ctypes.data
-            d.num_levels, d.level_dim, d.base_resolution = enc.num_levels, enc.level_dim, enc.base_resolution
-            d.log2_per_level_scale = float(np.log2(enc.per_level_scale))
+            self._fill_grid(d, emb.data_ptr())
             self._grid_desc, self._grid_desc_key = d, key
         return self._grid_desc
 
@@ -456,23 +461,15 @@ class MLP(nn.Module):
         """A copy of `grid_field()` with the unpacked density_layer pointers: what the density-normal kernels read
         (ucn_density_feature_grad recomputes the hidden layer in fp32 from them).  No packed stream: the training
         route uses it every step.  The caller keeps it alive for the launches it makes with it."""
-        d = _lib.UcnField()
-        ctypes.memmove(ctypes.byref(d), ctypes.byref(self.grid_field()), ctypes.sizeof(_lib.UcnField))
+        grid = self.grid_field()
         ws = [self.density_layer[0].weight, self.density_layer[0].bias, self.density_layer[2].weight, self.density_layer[2].bias]
-        for w in ws:
-            _lib.require_device(w, f"{type(self).__name__} parameter")
-            if w.dtype != torch.float32 or not w.is_contiguous():
-                raise RuntimeError("field parameters must be contiguous float32")
-        d.w_d0, d.b_d0, d.w_d1, d.b_d1 = (w.data_ptr() for w in ws)
-        return d
+        _require_f32(ws, f"{type(self).__name__} parameter")
+        return _field_copy(grid, **{k: w.data_ptr() for k, w in zip(('w_d0', 'b_d0', 'w_d1', 'b_d1'), ws)})
 
     def grid_field_with(self, embeddings):
         """A copy of `grid_field()` that reads another table of the same layout: the half-precision copy of an autocast pass
         (gridencoder/grid.py:41-44).  The caller keeps `embeddings` alive for as long as it uses the descriptor."""
-        d = _lib.UcnField()
-        ctypes.memmove(ctypes.byref(d), ctypes.byref(self.grid_field()), ctypes.sizeof(_lib.UcnField))
-        d.embeddings = embeddings.data_ptr()
-        return d
+        return _field_copy(self.grid_field(), embeddings=embeddings.data_ptr())
 
     # ---- reference API on explicit Gaussians (extract.py:56-57,96) ---------------------------
     @torch.no_grad()
