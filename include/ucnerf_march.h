@@ -557,7 +557,8 @@ int ucn_ray_film_backward(const void *gy, const void *x, const float *a, void *g
 /* Training-time forward of the NeRF field's dense layers in one kernel (models.py:507-674 under
  * accelerator.autocast(): bf16 operands, fp32 accumulation), writing every activation the backward needs once:
  * h0 [M,64], x [M,256] (bottleneck), h1, h2 [M,256] as bf16, raw [M] = x[:,0], y [M,3] = pre-sigmoid colour, M = N*S,
- * and the ReLU masks m0 / m1 / m2 (16 bits per 32-feature tile and wave half) for ucn_train_bwd.
+ * and the ReLU masks m0 / m1 / m2 (16 bits per 32-feature tile and wave half) for ucn_train_bwd.  A mask bit is the sign of the
+ * fp32 pre-activation (set = sign clear): a pre-activation of exactly +0 stores the activation 0 AND a set bit (relu'(0) = 1).
  * packed = ucn_train_fwd_fragments() fragments of 64 lanes x 8 bf16 (1 KiB), of which the forward reads the first 256:
  * W_d0, W_d1, then the colour layers COMPOSED with the activation-free bottleneck -- (W0x W_d1) [256 x 64] and
  * [W1h | W1x W_d1] [256 x 320] -- and W_rgb woven behind each output-tile pair of the last hidden layer, all in MFMA

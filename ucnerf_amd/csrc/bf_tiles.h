@@ -105,9 +105,10 @@ __device__ __forceinline__ void tile_pair_pf(RING &ring, bf8 (&wp)[kWSlots], f32
 // bit r = accumulator register r is positive (the ReLU mask of the lane's 16 features of a tile).  One v_alignbit_b32 per
 // register shifts its SIGN bit into the word ((m << 1) | sign), registers taken from 15 down to 0, then one inversion: 17 VALU
 // instructions per tile where compare + select + or took 48 (the training kernels' masks were 2700 of the sky forward's 5600
-// VALU instructions per wave).  A pre-activation of exactly +0 counts as positive (torch: gradient 0 there): a set of
-// measure zero -- MFMA accumulation from a +0 / bias start cannot produce -0, and a bias that cancels a dot product exactly
-// does not occur in practice.
+// VALU instructions per wave).  A pre-activation of exactly +0 counts as positive: relu'(0) = 1 here, a valid subgradient
+// where torch picks 0.  MFMA accumulation from a +0 / bias start cannot produce -0; a bias that cancels a dot product exactly
+// is rare but real with bf16 operands and few terms (F = 1: feat w = -bias, tests/test_heads_layerwise_cpu.py) -- the stored
+// activation is 0 there and the bit is set, which the layer-wise tests allow only inside the fp32 error band around 0.
 __device__ __forceinline__ uint32_t mask16(const f32x16 &a) {
     uint32_t m = 0;
 #pragma unroll
