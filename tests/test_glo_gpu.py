@@ -123,7 +123,7 @@ def test_glo_forward_vs_golden(zero_glo):
 @pytest.mark.parametrize("zero_glo", [True, False])
 def test_glo_forward_vs_golden_under_autocast(zero_glo):
     """The same under bf16 autocast (the reference's render_image context).  zero_glo=True takes the mixed-precision fused march
-    (_mixed_level, folded weights); bars: bf16 through three 256-wide layers, those of
+    (march_infer.mixed_level, folded weights); bars: bf16 through three 256-wide layers, those of
     test_render_under_autocast_runs_the_mixed_precision_path."""
     fx = fixture("model_glo.npz")
     tag = "Z1_" if zero_glo else "Z0_"

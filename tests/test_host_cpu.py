@@ -426,6 +426,13 @@ def test_cached_rebuilds_when_a_parameter_changes_and_copies_drop_the_slots():
     nl.weight = torch.nn.Parameter(nl.weight.detach().clone())
     third = get()
     assert third is not second and len(builds) == 3 and get() is third
+    # an extra key (flags the value depends on): the same parameters under another extra key cause one rebuild
+    flagged = lambda flag: models._cached(mlp, "_pred_head", [nl.weight, nl.bias], build, extra=(flag,))
+    on = flagged(True)
+    assert on is not third and len(builds) == 4 and flagged(True) is on and len(builds) == 4
+    assert mlp._pred_head[0] == ((nl.weight.data_ptr(), nl.weight._version), (nl.bias.data_ptr(), nl.bias._version), True)
+    off = flagged(False)
+    assert off is not on and len(builds) == 5 and flagged(False) is off and len(builds) == 5
     for slot in ("_ref_head", "_glo_fold", "_level_scale"):
         models._cached(mlp, slot, [nl.bias], lambda: object())
     assert all(hasattr(mlp, s) for s in ("_pred_head", "_ref_head", "_glo_fold", "_level_scale"))

@@ -185,7 +185,7 @@ def test_forward_vs_golden(name, kind, mode):
 
 @pytest.mark.parametrize("name,kind", [("model_scalefeat.npz", "tiny"), ("model_scalefeat_R.npz", "tinyR")])
 def test_forward_under_autocast_takes_the_fp32_class_path(name, kind):
-    """Under bf16 autocast (render_image's context) a flag-on field does not take the mixed-precision kernels (_mixed_level
+    """Under bf16 autocast (render_image's context) a flag-on field does not take the mixed-precision kernels (march_infer.mixed_level
     returns None): the fused march on the fp32-class path, pixels within the fp32 bars of test_forward_vs_golden."""
     fx = fixture(name)
     spec = rm.make_spec(kind)

@@ -309,7 +309,7 @@ def test_unwarped_scale_featurization_inference_and_training_routes():
 # ---------------------------------------------------------------------------------------------------- 4. other routes
 def test_unwarped_render_image_compaction_and_mixed_precision():
     """test_warped_render_image_and_compaction_match_the_forward on an unwarped model, then the mixed-precision inference
-    (Model._mixed_level under bf16 autocast) against the fp32-class march with the bars of
+    (march_infer.mixed_level under bf16 autocast) against the fp32-class march with the bars of
     test_glo_forward_vs_golden_under_autocast (bf16 through three 256-wide layers: 3e-2 max, 3e-3 mean)."""
     from ucnerf_amd.internal import models
     spec = rm.make_spec("tiny")

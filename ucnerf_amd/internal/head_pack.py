@@ -1,5 +1,5 @@
 """What the bf16 dense kernels read of a field's parameters (MFMA fragment streams, accumulator-order vectors, the view encoding): no
-autograd; heads_bf16.py packs through it for training, `Model._mixed_level` (models.py) for the mixed-precision inference march."""
+autograd; heads_bf16.py packs through it for training, `mixed_level` (march_infer.py) for the mixed-precision inference march."""
 import torch
 
 from .. import _lib

@@ -1,8 +1,9 @@
-"""What a sampling level needs around its kernels, once for both marches (ref models.py:97-324): `Model._march` (models.py, the
+"""What a sampling level needs around its kernels, once for both marches (ref models.py:97-324): `march` (march_infer.py, the
 fused inference march) and `march_train` (train_graph.py, the autograd march; its nodes: march_nodes.py) walk the same level schedule.  Here: the batch's
 rays, the level plan and anneal value, the random draws in the reference's order, a level's fenceposts with the choice between
-an entry point and its `_tdist` sibling, and the result dictionaries.  What runs in between -- featurisation, dense layers,
-compositing, the sky and brightness tails -- stays with each march (kernels in one, autograd nodes in the other)."""
+an entry point and its `_tdist` sibling, the inference march's pass plan, and a level's outputs with the result dictionaries made of them.
+What runs in between -- featurisation, dense layers, compositing, the sky and brightness tails -- stays with each march (kernels in one,
+autograd nodes in the other)."""
 import ctypes
 import functools
 
@@ -72,6 +73,22 @@ def level_plan(model, train_frac=None):
         prod_num_samples *= S
         plan.append((i_level, is_prop, S, mlp, dilation))
     return plan
+
+
+def pass_plan(N, nerf_chunk, level_row, nerf_row, is_prop):
+    """(chunk, [(i_pass, r0, n)]): the inference march's passes over a level's N rays, `chunk` rays each and the rest in the last.
+    nerf_chunk = Model.max_chunk_rays is quoted for the NeRF level (nerf_row feature floats per ray); a proposal level with a shorter row
+    (level_row: fewer samples, narrower features) takes proportionally more rays per pass -- the same workspace bytes, fewer and longer
+    launches -- in multiples of 256, at most 65536."""
+    chunk = nerf_chunk
+    if is_prop and level_row < nerf_row:
+        chunk = max(nerf_chunk, min(nerf_chunk * nerf_row // level_row // 256 * 256, 1 << 16))
+    return chunk, [(i_pass, r0, min(chunk, N - r0)) for i_pass, r0 in enumerate(range(0, N, chunk))]
+
+
+def timed_pass(i_pass, prof_every):
+    """whether pass i_pass gets timing events (Model._prof): one of every prof_every passes, from the middle of each group"""
+    return i_pass % prof_every == prof_every // 2
 
 
 def draws(rays, i_level, S, rand, single_jitter):
@@ -314,3 +331,40 @@ def history_entry(coord, density, rgbs, sdist, weights, prefix, raw_grad=None, n
                 normals_pred=None if normals_pred is None else normals_pred.reshape(prefix + (S, 3)),
                 roughness=None if roughness is None else roughness.reshape(prefix + (S, 1)),
                 sdist=sdist.reshape(prefix + (S + 1,)).clone(), weights=weights.reshape(prefix + (S,)).clone())
+
+
+class LevelOutputs:
+    """What one level of either march produces: per sample density [N, S], rgbs [N, S, 3] (None: a field without colour layers), weights
+    [N, S], coord, raw_grad, normals, grad_pred, normals_pred [N, S, 3], roughness [N, S] or [N, S, 1]; per ray main = the composited
+    (rgb, depth, acc) -- the compositing kernel's [N, 5] buffer, or the three tensors of the autograd nodes -- and extras [N, 4].  None =
+    not produced.  The one place that turns them into the result dictionaries."""
+    __slots__ = ("density", "rgbs", "weights", "main", "extras", "coord", "raw_grad", "normals", "grad_pred", "normals_pred", "roughness")
+
+    def __init__(self, **outputs):
+        for k in self.__slots__:
+            setattr(self, k, outputs.pop(k, None))
+        assert not outputs, sorted(outputs)
+
+    @classmethod
+    def allocate(cls, mlp, N, S, dev, want_history, compute_extras):
+        """The buffers the inference march's kernels fill for `mlp`'s level: colours with the field's colour layers (the NeRF level's, and
+        those of a proposal field built with PropMLP.disable_rgb = False, which the reference composites like the last level's,
+        models.py:221-283); extras with compute_extras; coord with want_history; density normals, predicted normals (7h)
+        and roughness (7i) where the field has them and something returns them (the history, or the renderings' extras)."""
+        buf = lambda want, *shape: torch.empty(N, *shape, device=dev) if want else None
+        returned = want_history or compute_extras
+        normals = (not mlp.disable_density_normals) and returned
+        pred = mlp.enable_pred_normals and returned
+        rough = bool(mlp.ref_heads_mask() & mlp.HEAD_ROUGHNESS) and returned
+        return cls(density=buf(True, S), rgbs=buf(not mlp.disable_rgb, S, 3), weights=buf(True, S), main=buf(True, 5),
+                   extras=buf(compute_extras, 4), coord=buf(want_history, S, 3), raw_grad=buf(normals, S, 3), normals=buf(normals, S, 3),
+                   grad_pred=buf(pred, S, 3), normals_pred=buf(pred, S, 3), roughness=buf(rough, S))
+
+    def rendering(self, prefix, sdist, n_vis):
+        rgb, depth, acc = self.main if isinstance(self.main, tuple) else (self.main[:, 0:3], self.main[:, 3], self.main[:, 4])
+        return rendering_entry(rgb, depth, acc, self.weights, self.extras, prefix, sdist, self.rgbs, n_vis, normals=self.normals,
+                               normals_pred=self.normals_pred, roughness=self.roughness)
+
+    def history(self, prefix, sdist):
+        return history_entry(self.coord, self.density, self.rgbs, sdist, self.weights, prefix, self.raw_grad, self.normals,
+                             grad_pred=self.grad_pred, normals_pred=self.normals_pred, roughness=self.roughness)

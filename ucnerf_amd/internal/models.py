@@ -16,7 +16,7 @@ torch.reciprocal / log / exp / sqrt / square; DESIGN.md "Ray-distance curves") a
 predicted-normal head (MLP.enable_pred_normals) and the Ref-NeRF colour heads (MLP.use_diffuse_color, use_specular_tint,
 enable_pred_roughness).
 Anything else raises at construction.
-In eval mode or with gradients disabled forward is the fused inference march; a model in training mode
+In eval mode or with gradients disabled forward is the fused inference march (internal/march_infer.py `march`); a model in training mode
 with gradients enabled routes to internal/train_graph.py `march_train` (same kernels for resampling and featurisation, HIP
 backward for the tables and the dense layers' dgrad, autograd glue; `Model.march_route`).  Without the HIP library or a GPU every entry point raises.
 """
@@ -29,7 +29,7 @@ import torch.nn as nn
 from .. import _lib
 from ..gridencoder import GridEncoder
 from . import march_level as ml
-from .head_pack import prepare_heads, rgb_activation, view_encoding
+from .head_pack import rgb_activation, view_encoding
 from .extrinsic_optimizer import BrightnessCorrection
 from .march_level import _f32, _u_table  # noqa: F401  (_u_table: not used here, kept importable for tests and tools)
 from .sky import NeRF, render_rays  # noqa: F401  (names kept importable like upstream)
@@ -74,10 +74,10 @@ def glo_fold(W0, b0, W1, b1, a, b):
     return W0f, b0 + W0x @ b, W1f, b1 + W1x @ b
 
 
-def _cached(obj, slot, params, build):
+def _cached(obj, slot, params, build, extra=()):
     """build()'s value, kept on `obj` as `slot` = (key, value) and rebuilt only when one of `params` was updated in place or
-    replaced: key = their (data_ptr, _version)."""
-    key = tuple((p.data_ptr(), p._version) for p in params)
+    replaced, or `extra` (flags the value depends on) changed: key = their (data_ptr, _version), then extra."""
+    key = tuple((p.data_ptr(), p._version) for p in params) + tuple(extra)
     hit = getattr(obj, slot, None)
     if hit is None or hit[0] != key:
         hit = (key, build())
@@ -770,290 +770,9 @@ class Model(nn.Module):
         cam_idx = batch['cam_idx'][..., 0]
         return self.glo_vecs(cam_idx.long()).reshape(N, self.num_glo_features)
 
-    def _mixed_level(self, mlp, is_prop, F_in):
-        """Mixed-precision inference of one level (see `autocast_render`): None = the fp32-class path, else what the bf16
-        kernels need -- the half table behind a copy of the grid descriptor and the packed / rounded dense parameters."""
-        if not (self.autocast_render and torch.is_autocast_enabled() and torch.get_autocast_dtype('cuda') == torch.bfloat16):
-            return None
-        if mlp.scale_featurization:                # the bf16 inference kernels read grid planes only: fp32-class path (DESIGN.md 7c)
-            return None
-        if not mlp.disable_density_normals:        # the normals pass reads fp32 features of the fp32 table: fp32-class path (DESIGN.md 7d)
-            return None
-        if mlp.enable_pred_normals:                # the head's kernel reads the fp32 feature buffer: fp32-class path (DESIGN.md 7h)
-            return None
-        if mlp.ref_heads_mask():                   # the same for the Ref-NeRF colour heads (DESIGN.md 7i)
-            return None
-        from .train_graph import heads_route
-        emb = mlp.encoder.embeddings
-        # the level's bf16 kernels are the training step's: the same route decision (no GLO here: every inference march is zero_glo)
-        if heads_route(mlp, F_in, emb.is_cuda, torch.bfloat16, None) != ("prop_fused" if is_prop else "fused_bf16"):      # (the features are fp32)
-            return None
-        # the half table and the packed weights are rebuilt only when a parameter changed (a frame is tens of chunks)
-        key = tuple((p.data_ptr(), p._version) for p in mlp.parameters()) + (bool(self.autocast_bf16_features),)
-        cache = self.__dict__.setdefault('_mixed_cache', {})
-        hit = cache.get(id(mlp))
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        out = {}
-        half = mlp.encoder.level_dim % 2 == 0                      # grid.py:41-44: half tables when C is even
-        if half:
-            out['table'] = emb.detach().to(torch.half)
-        out['desc'], out['table_flag'] = mlp.grid_field_with(out['table'] if half else emb), (_lib.TABLE_F16 if half else 0)
-        # the NeRF level's features leave the gather as the bf16 pairs its MLP consumes (half the workspace traffic)
-        out['feat_flag'] = _lib.FEATURES_BF16 if (half and mlp.encoder.level_dim == 2 and not is_prop and self.autocast_bf16_features) else 0
-        with torch.autocast('cuda', enabled=False):
-            if is_prop:
-                l0, l1 = mlp.density_layer[0], mlp.density_layer[2]
-                out['prop'] = tuple(t.detach().float().contiguous() for t in (l0.weight, l0.bias, l1.weight, l1.bias))
-            else:
-                d0, d1, c0, c1, lr = mlp.density_layer[0], mlp.density_layer[2], mlp.lin_second_stage_0, mlp.lin_second_stage_1, mlp.rgb_layer
-                # a GLO field: the zero code's modulation folded into the colour layers (every inference march here is zero_glo)
-                W0, b0, W1, b1 = mlp._glo_folded() if mlp.uses_glo() else (c0.weight, c0.bias, c1.weight, c1.bias)
-                packed, _, We, be, bias0, bias1, biasr = prepare_heads(d0.weight, d0.bias, d1.weight, d1.bias, W0, b0,
-                                                                      W1, b1, lr.weight, lr.bias, dir_in_stream=True)
-                out.update(packed=packed, We=We, be=be, bias0=bias0, bias1=bias1, biasr=biasr, NW=c0.weight.shape[0],
-                           head=(ctypes.c_float * 4)(float(mlp.density_bias), float(mlp.rgb_premultiplier), float(mlp.rgb_bias),
-                                                     float(mlp.rgb_padding)),
-                           enc=lambda v: _dir_tiles(view_encoding(v.float(), mlp.deg_view)))
-        cache[id(mlp)] = (key, out)
-        return out
-
-    def _mlp_route(self, *, mlp, is_prop, S, desc, mixed, rays, posts, dirb, co, compact, density, rgbs, weights, main, nc):
-        """The level's dense layers as one callable run(fb, sl, r0, n): density (and colours) of the n rays `sl` = [r0, r0 + n) from the
-        feature buffer `fb`.  Chosen once per level: mixed-precision proposal / NeRF level, compacted colour pass, plain ucn_field_mlp."""
-        lib, st, dev = _lib.load(), _lib.stream(), rays.dev
-        L, C = mlp.encoder.num_levels, mlp.encoder.level_dim
-        dir_row = dirb.numel() // max(rays.N, 1)            # (an empty batch runs no pass)
-        rf = int(bool(self.rays_fastest))
-        if mixed is not None and is_prop:
-            w0, b0_, w1, b1_ = mixed['prop']
-            def run(fb, sl, r0, n):
-                _lib.check(lib.ucn_prop_train_fwd(fb.data_ptr(), L * C, w0.shape[0], w0.data_ptr(), b0_.data_ptr(), w1.data_ptr(),
-                                                  b1_.data_ptr(), float(mlp.density_bias), 1, n * S, density[sl].data_ptr(), n, C, st))
-        elif mixed is not None:
-            # the ray's direction tile rides in the weight stream's last input tile (no per-ray terms to pre-multiply)
-            vd_enc = mixed['enc'](rays.vd)
-            feat_flags = C | (_lib.FEAT_BF16 if mixed['feat_flag'] else 0)
-            def run(fb, sl, r0, n):
-                _lib.check(lib.ucn_train_fwd(fb.data_ptr(), L * C, mixed['packed'].data_ptr(), mixed['bias0'].data_ptr(),
-                                             mixed['bias1'].data_ptr(), mixed['biasr'].data_ptr(), None, None, n, S,
-                                             None, None, None, None, 0, vd_enc[sl].data_ptr(), None, None, mixed['head'],
-                                             density[sl].data_ptr(), rgbs[sl].data_ptr(), None, None, None, feat_flags, st))
-        elif compact:
-            composite = posts.entry(lib, 'ucn_composite')
-            bg, opaque = float(self.bg_intensity_range[0]), int(bool(self.opaque_background))
-            def run(fb, sl, r0, n):
-                # density head -> weights of this pass's rays -> alive list -> colour layers of the alive samples
-                _lib.check(lib.ucn_field_mlp(ctypes.byref(desc), fb.data_ptr(), n * S, S, rf, None, density[sl].data_ptr(),
-                                             None, None, st))
-                _lib.check(composite(density[sl].data_ptr(), None, *posts.compositing(sl), rays.d[sl].data_ptr(), bg, opaque,
-                                     n, S, weights[sl].data_ptr(), main[sl].data_ptr(), None, st))
-                if getattr(self, '_alive_idx', None) is None or self._alive_idx.numel() < n * S or self._alive_idx.device != dev:
-                    self._alive_idx = torch.empty(max(n, nc) * S, dtype=torch.int32, device=dev)
-                    self._alive_cnt = torch.zeros(1, dtype=torch.int32, device=dev)
-                _lib.check(lib.ucn_compact_alive(weights[sl].data_ptr(), n, S, rf, float(self.compact_min_weight),
-                                                 self._alive_idx.data_ptr(), self._alive_cnt.data_ptr(), st))
-                rgbs[sl].zero_()
-                _lib.check(lib.ucn_field_rgb_compacted(ctypes.byref(desc), fb.data_ptr(), n * S, S, rf,
-                                                       dirb[r0 * dir_row:].data_ptr(), self._alive_idx.data_ptr(),
-                                                       self._alive_cnt.data_ptr(), rgbs[sl].data_ptr(), st))
-                stats = getattr(self, '_alive_stats', None)
-                if stats is not None:                              # diagnostics (tools/alive_fraction.py): forces a sync
-                    stats.append((int(self._alive_cnt.item()), n * S))
-        else:
-            def run(fb, sl, r0, n):
-                _lib.check(lib.ucn_field_mlp(
-                    ctypes.byref(desc), fb.data_ptr(), n * S, S, rf | co,
-                    None if rgbs is None else dirb[r0 * dir_row:].data_ptr(),
-                    density[sl].data_ptr(), None if rgbs is None else rgbs[sl].data_ptr(), None, st))
-        return run
-
     def _march(self, rand, batch, train_frac, compute_extras, eval_camidx, want_history):
-        lib = _lib.load()
-        rays = ml.Rays(batch, self.num_levels)
-        N, dev, prefix = rays.N, rays.dev, rays.prefix
-        st = _lib.stream()
-        cfg = self.config
-        self.last_march_route = 'fused'       # diagnostics / tests: the route of the last forward (train_graph: 'train_graph')
-        nerf_desc = self.nerf_mlp.field(glo_fold=True)          # a GLO field: zero codes folded into the colour layers
-        dirb = torch.empty(lib.ucn_field_dir_floats(ctypes.byref(nerf_desc), N), device=dev)
-        _lib.check(lib.ucn_field_dir_bias(ctypes.byref(nerf_desc), rays.vd.data_ptr(), N, dirb.data_ptr(), st))
-
-        renderings, ray_history = [], []
-        posts = weights = None
-        gain = ml.ray_gain(self, batch, rays)                   # the RawNeRF exposure (None without batch['exposure_idx'])
-        nerf_chunk = max(1, int(self.max_chunk_rays))
-        planes = lambda m: m.encoder.num_levels + m.scale_planes()          # feature planes of level_dim floats per sample
-        nerf_row = self.num_nerf_samples * planes(self.nerf_mlp) * self.nerf_mlp.encoder.level_dim
-        for i_level, is_prop, S, mlp, dilation in ml.level_plan(self, train_frac):
-            desc = mlp.field(glo_fold=not is_prop)
-            L, C = mlp.encoder.num_levels, mlp.encoder.level_dim
-            # max_chunk_rays is quoted for the NeRF level; a proposal level (fewer samples, narrower features) takes
-            # proportionally more rays per pass -- the same workspace bytes, fewer and longer launches
-            chunk = nerf_chunk
-            if is_prop and S * planes(mlp) * C < nerf_row:
-                chunk = max(nerf_chunk, min(nerf_chunk * nerf_row // (S * planes(mlp) * C) // 256 * 256, 1 << 16))
-            # ---- random draws and fenceposts (resample -> cone basis -> metric fenceposts of a warped raydist_fn)
-            posts, flip, spin = ml.fenceposts(self, rays, i_level, S, dilation, train_frac, rand, posts, weights, st)
-            # ---- outputs of the level
-            density = torch.empty(N, S, device=dev)
-            # colours: the NeRF level's, and those of a proposal field built with its colour layers (PropMLP.disable_rgb = False; the
-            # reference composites them like the last level's, models.py:221-283)
-            rgbs = None if mlp.disable_rgb else torch.empty(N, S, 3, device=dev)
-            level_dirb = dirb
-            if is_prop and rgbs is not None:
-                level_dirb = torch.empty(lib.ucn_field_dir_floats(ctypes.byref(desc), N), device=dev)
-                _lib.check(lib.ucn_field_dir_bias(ctypes.byref(desc), rays.vd.data_ptr(), N, level_dirb.data_ptr(), st))
-            weights = torch.empty(N, S, device=dev)
-            main = torch.empty(N, 5, device=dev)
-            extras = torch.empty(N, 4, device=dev) if compute_extras else None
-            coord = torch.empty(N, S, 3, device=dev) if want_history else None
-            # density normals (DESIGN.md 7d): for every sample (compacted or not), when something returns them
-            want_normals = (not mlp.disable_density_normals) and (want_history or compute_extras)
-            raw_grad = torch.empty(N, S, 3, device=dev) if want_normals else None
-            normals = torch.empty(N, S, 3, device=dev) if want_normals else None
-            normals_field = mlp.normals_field() if want_normals else None          # once per level, not per pass
-            # predicted normals (DESIGN.md 7h): for every sample (compacted or not), when something returns them
-            want_pred = mlp.enable_pred_normals and (want_history or compute_extras)
-            grad_pred = torch.empty(N, S, 3, device=dev) if want_pred else None
-            normals_pred = torch.empty(N, S, 3, device=dev) if want_pred else None
-            pred_head = mlp.pred_head() if want_pred else None                     # once per level, not per pass
-            # the Ref-NeRF colour heads (DESIGN.md 7i): the diffuse head changes the colours, so its pass always runs (for every sample,
-            # compacted or not); the roughness only when something returns it.  The dense layers then leave the plain sigmoid
-            ref_mask = mlp.ref_heads_mask()
-            want_rough = bool(ref_mask & mlp.HEAD_ROUGHNESS) and (want_history or compute_extras)
-            want_ref = bool(ref_mask & mlp.HEAD_DIFFUSE) or want_rough
-            roughness = torch.empty(N, S, device=dev) if want_rough else None
-            ref_head = mlp.ref_head() if want_ref else None                        # once per level, not per pass
-            mlp_desc = mlp.unpadded_field(desc) if ref_mask & mlp.HEAD_DIFFUSE else desc
-            nc = min(chunk, N)
-            feat = torch.empty(planes(mlp) * nc * S * C, device=dev)
-            level_scale = mlp.level_scale() if mlp.scale_featurization else None
-            mixed = self._mixed_level(mlp, is_prop, L * C)
-            self._mixed_levels = getattr(self, '_mixed_levels', 0) + (mixed is not None)      # diagnostics / tests
-            prof = getattr(self, '_prof', None)
-            prof_every = max(1, int(getattr(self, '_prof_every', 1)))
-            # Two HIP streams: featurisation of pass i+1 (L2-request / VALU bound) runs beside the MLP of pass i
-            # (MFMA bound) on a second feature buffer; the hardware splits the CUs between the two kernels.
-            overlap = bool(self.overlap_streams) and N > chunk
-            co = _lib.LAUNCH_CORESIDENT if (overlap and not is_prop and self.overlap_streams != 2) else 0     # launch shapes that share a CU (2: plain shapes, tails only)
-            compact = (not is_prop) and (not want_history) and self.compact_min_weight > 0 and mlp.mlp_mode == 1 and mixed is None
-            run_mlp = self._mlp_route(mlp=mlp, is_prop=is_prop, S=S, desc=mlp_desc, mixed=mixed, rays=rays, posts=posts, dirb=level_dirb, co=co,
-                                      compact=compact, density=density, rgbs=rgbs, weights=weights, main=main, nc=nc)
-            feat_desc = ctypes.byref(desc if mixed is None else mixed['desc'])
-            feat_layout = ((2 if self.rays_fastest else 0) | co) if mixed is None else (2 | mixed['table_flag'] | (mixed['feat_flag'] if not is_prop else 0))
-            cur = torch.cuda.current_stream()
-            feats = [feat]
-            if overlap:
-                feats.append(torch.empty_like(feat))
-                if getattr(self, '_side_stream', None) is None:
-                    self._side_stream = torch.cuda.Stream()
-                side = self._side_stream
-                side.wait_stream(cur)
-            mlp_done = [None, None]
-            for i_pass, r0 in enumerate(range(0, N, chunk)):
-                n = min(chunk, N - r0)
-                sl = slice(r0, r0 + n)
-                fb = feats[i_pass % len(feats)]
-                # (bench.py's live per-kernel times: HIP events around every `_prof_every`-th pass only -- an event record costs the queue
-                #  ~10 us of idle time at a kernel boundary; around every pass that was 9 ms of a 470 ms frame, tools/frame_gaps.py)
-                timed = prof is not None and i_pass % prof_every == prof_every // 2
-                if timed:
-                    e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
-                    m0 = torch.cuda.Event(enable_timing=True) if overlap else e1       # one stream: the MLP starts where the gather ends
-                fstream = side if overlap else cur
-                if overlap and mlp_done[i_pass % 2] is not None:
-                    side.wait_event(mlp_done[i_pass % 2])             # the buffer's previous reader
-                if timed:
-                    e0.record(fstream)
-                _lib.check(posts.ray_call(
-                    lib, 'ucn_march_features', feat_desc, rays, flip, spin, sl, self.std_scale, mlp.warp, n, S, int(self.levels_per_block),
-                    feat_layout, fb.data_ptr(), None if coord is None else coord[sl].data_ptr(), None, fstream.cuda_stream))
-                if level_scale is not None:          # the scale planes of this pass's n * S samples, behind its L grid planes
-                    _lib.check(posts.ray_call(
-                        lib, 'ucn_march_scale_features', feat_desc, rays, flip, spin, sl, self.std_scale, mlp.warp, n, S,
-                        level_scale.data_ptr(), feat_layout & 3, fb[L * n * S * C:].data_ptr(), fstream.cuda_stream))
-                if timed:
-                    e1.record(fstream)
-                if overlap:
-                    ready = torch.cuda.Event()
-                    ready.record(side)
-                    cur.wait_event(ready)
-                if timed and overlap:
-                    m0.record(cur)
-                run_mlp(fb, sl, r0, n)
-                if want_ref:                          # behind the MLP, on its stream, before anything rewrites the pass's feature buffer
-                    ml.ref_heads(mlp, desc, ref_head, fb, sl, n, S, feat_layout & 3, rgbs, roughness, st)
-                if want_normals:                      # behind the MLP, on its stream: the pass's feature buffer becomes gfeat
-                    # (with _prof set, e2 below closes after it: the pass's "MLP" time then includes the normals pass)
-                    ml.density_normals(mlp, posts, rays, flip, spin, sl, n, S, self.std_scale, feat_layout & 3, fb, raw_grad, normals, st,
-                                       field=normals_field)
-                if want_pred:                         # behind the MLP, on its stream: reads the pass's feature buffer, which the MLP left intact
-                    ml.pred_normals(desc, pred_head, fb, sl, n, S, feat_layout & 3, grad_pred, normals_pred, st)
-                if overlap:
-                    mlp_done[i_pass % 2] = torch.cuda.Event()
-                    mlp_done[i_pass % 2].record(cur)
-                if timed:
-                    e2.record(cur)
-                    prof.append((i_level, n, e0, e1, m0, e2))      # features: e0..e1 on its stream, MLP: m0..e2
-            if overlap:
-                cur.wait_stream(side)
-            # the level's background colours (drawn behind its MLP, models.py:256), then one launch: `rgbs` leaves it scaled by the gain
-            bg, ray_bg = ml.background(self, rays, i_level, rand)
-            ml.composite(posts, density, rgbs, rays.d, gain, ray_bg, bg, self.opaque_background, weights, main, extras, st)
-            renderings.append(ml.rendering_entry(main[:, 0:3], main[:, 3], main[:, 4], weights, extras, prefix, posts.sdist, rgbs,
-                                                 getattr(cfg, 'vis_num_rays', 16), normals=normals, normals_pred=normals_pred,
-                                                 roughness=roughness))
-            if want_history:
-                ray_history.append(ml.history_entry(coord, density, rgbs, posts.sdist, weights, prefix, raw_grad, normals,
-                                                    grad_pred=grad_pred, normals_pred=normals_pred, roughness=roughness))
-
-        if compute_extras:                                             # ref models.py:313-324
-            ml.broadcast_final(renderings)
-
-        o, d, cam, far = rays.o, rays.d, rays.cam, rays.far
-        if getattr(cfg, 'model_sky', False):                           # ref models.py:326-337
-            # inference under an active bf16 autocast: the sky NeRF's nn.Linear layers are bf16 in the reference
-            sky_mixed = bool(self.autocast_render and torch.is_autocast_enabled()
-                             and torch.get_autocast_dtype('cuda') == torch.bfloat16)
-            self._sky_mixed = sky_mixed
-            if self.sky_min_background > 0 and not rand:
-                bgw = 1 - renderings[-1]['weights'].reshape(N, -1).sum(dim=-1)
-                keep = torch.nonzero(bgw >= self.sky_min_background).reshape(-1)      # host sync, like far[0] in render()
-                sky = torch.zeros(N, 3, device=dev)
-                if keep.numel() == N:
-                    sky = self.skynerf.render(o, d, cam, far, mixed=sky_mixed)
-                elif keep.numel():
-                    # far0 = 1.5 * far[0] of the FULL batch (models.py:329), not of the kept rays
-                    sky[keep] = self.skynerf.render(o[keep], d[keep], cam[keep], far[keep], far0=far.reshape(-1)[:1], mixed=sky_mixed)
-                self._sky_kept = (int(keep.numel()), N)
-            else:
-                sky = self.skynerf.render(o, d, cam, far, mixed=sky_mixed)
-            for r in renderings:
-                r['sky_rgbs'] = sky
-        if getattr(cfg, 'brightness_correction', False):               # ref models.py:339-363
-            with_sky = getattr(cfg, 'model_sky', False)
-            if eval_camidx is None:
-                cam_idx = batch['cam_idx'].reshape(N, -1)[:, 0]
-            else:
-                cam_idx = torch.as_tensor(eval_camidx).to(dev).reshape(-1)[:1]
-            A, A_sky, row_of = self.brightness_corr.affines(cam_idx)
-            last_w = renderings[-1]['weights'].reshape(N, -1)          # loop-leaked `rendering` (Appendix C.3)
-            for r in renderings:
-                rgb_in = r['rgb'].reshape(N, 3).contiguous()
-                rgb_out = torch.empty(N, 3, device=dev)
-                _lib.check(lib.ucn_apply_affine(rgb_in.data_ptr(), A.data_ptr(), _lib.ptr(row_of),
-                                                last_w.data_ptr() if with_sky else None, last_w.shape[1],
-                                                r['sky_rgbs'].data_ptr() if with_sky else None,
-                                                _lib.ptr(A_sky), N, rgb_out.data_ptr(), st))
-                # ref :356-359: [N,1,1,3] for training batches, [N,3] with eval_camidx
-                r['rgb'] = rgb_out.reshape(N, 1, 1, 3) if eval_camidx is None else rgb_out
-                full = A if row_of is None else A[row_of]
-                r['affine_trans'] = full.reshape(-1, 3, 4).expand(N, 3, 4)
-                if with_sky:
-                    full_s = A_sky if row_of is None else A_sky[row_of]
-                    r['affine_trans_sky'] = full_s.reshape(-1, 3, 4).expand(N, 3, 4)
-        return renderings, ray_history
+        from . import march_infer          # the fused inference march (imported on first use, like train_graph)
+        return march_infer.march(self, rand, batch, train_frac, compute_extras, eval_camidx, want_history)
 
 
 import contextlib
@@ -1095,16 +814,6 @@ def unwrap_model(model):
     if not hasattr(model, '_march'):
         raise TypeError(f"render_image: expected a ucnerf_amd Model (possibly DDP-wrapped), got {type(model).__name__}")
     return model
-
-
-def _dir_tiles(enc):
-    """[N, E <= 31] direction encodings -> [N, 32] bf16 tiles [enc, 1, 0...]: the input tile whose column E meets the bias column
-    of the colour layers' weight streams (head_pack._head_gather_index(dir_in_stream=True))."""
-    n, e = enc.shape
-    t = torch.zeros(n, 32, device=enc.device, dtype=torch.bfloat16)
-    t[:, :e] = enc
-    t[:, e] = 1.0
-    return t
 
 
 _TILE_ORDER = {}

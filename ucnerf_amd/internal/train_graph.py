@@ -322,10 +322,10 @@ def march_train(model, rand, batch, train_frac, compute_extras, eval_camidx, glo
                 gfeat = feat.detach()[:, :L * C].float().reshape(N * S, L, C).permute(1, 0, 2).contiguous()
                 raw_grad, normals = torch.empty(N, S, 3, device=dev), torch.empty(N, S, 3, device=dev)
                 ml.density_normals(mlp, posts, rays, flip, spin, slice(None), N, S, model.std_scale, 0, gfeat, raw_grad, normals, st)
-        renderings.append(ml.rendering_entry(c_rgb, c_depth, c_acc, weights, extras, prefix, posts.sdist, rgbs, getattr(cfg, 'vis_num_rays', 16),
-                                             normals=normals, normals_pred=normals_pred, roughness=roughness))
-        hist = ml.history_entry(coord, density, rgbs, posts.sdist, weights, prefix, raw_grad, normals, grad_pred=grad_pred,
-                                normals_pred=normals_pred, roughness=roughness)
+        out = ml.LevelOutputs(density=density, rgbs=rgbs, weights=weights, main=(c_rgb, c_depth, c_acc), extras=extras, coord=coord, raw_grad=raw_grad,
+                              normals=normals, grad_pred=grad_pred, normals_pred=normals_pred, roughness=roughness)
+        renderings.append(out.rendering(prefix, posts.sdist, getattr(cfg, 'vis_num_rays', 16)))
+        hist = out.history(prefix, posts.sdist)
         if model.training:
             hist['loss_hash_decay'] = hash_decay(mlp)
         ray_history.append(hist)
