@@ -22,6 +22,7 @@
 #ifndef UCNERF_MARCH_H
 #define UCNERF_MARCH_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -803,6 +804,21 @@ int ucn_marching_cubes_emit(const float *volume, uint32_t X, uint32_t Y, uint32_
  * pred, gt [H, W, 3] float32 in [0, 1] (DEVICE) -> out[0] = psnr (dB), out[1] = ssim, out[2] = mse on the uint8 scale (DEVICE doubles). */
 uint64_t ucn_image_metrics_ws_bytes(uint32_t H, uint32_t W);
 int ucn_image_metrics(const float *pred, const float *gt, uint32_t H, uint32_t W, void *workspace, double *out, ucn_stream_t stream);
+
+/* Colour correction of a frame against its ground truth (added within ABI 32; ref: internal/image.py:71-111 color_correct, three channels).
+ * img, ref [n_pixels][3] float32 (DEVICE).  Per iteration and channel c: least squares of ref[c] on the quadratic row
+ * [r r, r g, r b, g g, g b, b b, r, g, b, 1] of the current image over the rows with unclipped(img[c]) & unclipped(cur[c]) &
+ * unclipped(ref[c]), unclipped(z) = eps <= z <= 1 - eps; then cur <- clip(row . warp, 0, 1).  out [n_pixels][3] = the last cur; warps
+ * [num_iters][10][3] (or NULL) = every iteration's solution.  The normal equations are accumulated and solved in double, with no atomics:
+ * bit-reproducible.  status (DEVICE, one word): bit c is set when channel c's system was rank deficient (a pivot not positive beyond
+ * rounding) or gave a non-finite warp; the bits are those of the first iteration in which any channel failed (its estimate is
+ * garbage clipped to [0, 1] -- a NaN clips to 0 -- so every later system, sharing the row, fails after it) and out is then meaningless; the call itself still returns 0.  num_iters + 1
+ * streaming launches and num_iters solves on `stream`, no host synchronisation.  n_pixels = 0 and num_iters = 0 (out = img) are legal.
+ * out must not alias img or ref.  workspace: ucn_colour_correct_ws_bytes(n_pixels) bytes of DEVICE memory. */
+size_t ucn_colour_correct_ws_bytes(uint32_t n_pixels);
+int ucn_colour_correct(const float *img, const float *ref, uint32_t n_pixels, uint32_t num_iters, float eps, void *workspace,
+                       float *out /*[n_pixels][3]*/, float *warps /*[num_iters][10][3] or NULL*/, int32_t *status /*DEVICE, 1 word*/,
+                       ucn_stream_t stream);
 
 /* generic small dense layer y = act(x W^T + b), used for the brightness MLP (4->256->256->256->12) */
 int ucn_dense(const float *x /*[M,K]*/, const float *w /*[Nout,K]*/, const float *b, uint32_t M,

@@ -193,6 +193,9 @@ SIGNATURES = {
     "ucn_marching_cubes_emit": [c_vp, c_u32, c_u32, c_u32, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp],
     "ucn_image_metrics_ws_bytes": [c_u32, c_u32],
     "ucn_image_metrics": [c_vp, c_vp, c_u32, c_u32, c_vp, c_vp, c_vp],
+    # image.color_correct on the device (added within ABI 32)
+    "ucn_colour_correct_ws_bytes": [c_u32],
+    "ucn_colour_correct": [c_vp, c_vp, c_u32, c_u32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp],
     "ucn_dense": [c_vp, c_vp, c_vp, c_u32, c_u32, c_u32, c_i32, c_vp, c_vp],
     "ucn_apply_affine": [c_vp, c_vp, c_vp, c_vp, c_u32, c_vp, c_vp, c_u32, c_vp, c_vp],
     "ucn_affine_blend": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
@@ -205,7 +208,7 @@ SIGNATURES = {
 _RESTYPES = {"ucn_last_error": ctypes.c_char_p, "ucn_abi_version": c_u32, "ucn_field_packed_floats": c_u64,
              "ucn_field_dir_floats": c_u64, "ucn_march_features_backward_ws_floats": c_u64,
              "ucn_sky_packed_floats": c_u64, "ucn_sky_workspace_floats": c_u64, "ucn_train_fwd_fragments": c_u64,
-             "ucn_prop_train_bwd_ws_floats": c_u64, "ucn_sky_train_packed_bytes": c_u64, "ucn_wgrad_ws_floats": c_u64, "ucn_wgrad_f32_ws_floats": c_u64, "ucn_wgrad_h3_ws_floats": c_u64, "ucn_pack_h3_bytes": c_u64, "ucn_relu_bits_words": c_u64, "ucn_marching_cubes_ws_bytes": c_u64, "ucn_image_metrics_ws_bytes": c_u64, "ucn_sky_train_act_ld": c_u32,
+             "ucn_prop_train_bwd_ws_floats": c_u64, "ucn_sky_train_packed_bytes": c_u64, "ucn_wgrad_ws_floats": c_u64, "ucn_wgrad_f32_ws_floats": c_u64, "ucn_wgrad_h3_ws_floats": c_u64, "ucn_pack_h3_bytes": c_u64, "ucn_relu_bits_words": c_u64, "ucn_marching_cubes_ws_bytes": c_u64, "ucn_image_metrics_ws_bytes": c_u64, "ucn_colour_correct_ws_bytes": ctypes.c_size_t, "ucn_sky_train_act_ld": c_u32,
              "ucn_sky_train_grad_ld": c_u32}
 
 # Entry points added without an ABI bump: host-side probes that no product path calls.  An older build of the same ABI

@@ -1,10 +1,13 @@
-"""Image metrics on the device -- host side of `ucn_image_metrics`.
+"""Image metrics and colour correction on the device -- host side of `ucn_image_metrics` and `ucn_colour_correct`.
 
 `MetricHarness` has the call shape of the reference's (internal/image.py:114-133: `harness(rgb_pred, rgb_gt, name_fn)` ->
 {'psnr', 'ssim', 'lpips'}) but takes the rendered frame where `render_image` left it, as a device tensor (numpy arrays are
 uploaded), and computes PSNR and SSIM there in one pass each; the two floats are the only thing that crosses PCIe.  LPIPS
 is computed only when the third-party `lpips` package (and its downloaded VGG weights) is importable, exactly as upstream;
-otherwise the key is absent."""
+otherwise the key is absent.
+
+`color_correct` has the reference's name and signature (internal/image.py:71-111) and is the step eval.py runs between `render_image`
+and the second `MetricHarness` call: the frame stays on the device, and the only synchronisation is the read of one status word."""
 import ctypes
 
 import numpy as np
@@ -33,6 +36,40 @@ def image_metrics(rgb_pred, rgb_gt):
     _lib.check(lib.ucn_image_metrics(p.data_ptr(), g.data_ptr(), H, W, ws.data_ptr(), out.data_ptr(), _lib.stream()))
     psnr, ssim, _ = out.cpu().tolist()
     return psnr, ssim
+
+
+def color_correct(img, ref, num_iters=5, eps=0.5 / 255, *, return_warps=False):
+    """Warp `img` to match the colours of `ref` (image.py:71-111): `num_iters` rounds of a per-channel least-squares quadratic colour
+    transform over the pixels that are unclipped in `img`, in the current estimate and in `ref`.  [..., 3] device tensors (numpy arrays and
+    CPU tensors are uploaded) of any float dtype -> a float32 device tensor of `img`'s shape; with `return_warps` also the [num_iters, 10, 3]
+    solutions.  The result carries no autograd graph (the reference's is differentiable torch; eval.py, its one caller, runs it without
+    gradients).  A channel whose system is rank deficient (fewer than ten independent unclipped pixels) raises RuntimeError: the reference's
+    answer there depends on the lstsq driver."""
+    if img.shape[-1] != ref.shape[-1]:
+        raise ValueError(f'img\'s {img.shape[-1]} and ref\'s {ref.shape[-1]} channels must match')
+    if img.shape[-1] != 3:
+        raise NotImplementedError(f"color_correct: {img.shape[-1]} channels; the device path is written for 3")
+    lib = _lib.load()
+    dev = img.device if torch.is_tensor(img) and img.is_cuda else torch.device("cuda")
+    p = torch.as_tensor(img).to(dev).float().contiguous()
+    g = torch.as_tensor(ref).to(dev).float().contiguous()
+    n, num_iters = p.numel() // 3, int(num_iters)
+    if g.numel() != p.numel():
+        raise RuntimeError(f"color_correct: img has {n} pixels and ref {g.numel() // 3}")
+    if n >= 2 ** 32 or num_iters < 0:
+        raise RuntimeError(f"color_correct: {n} pixels, num_iters = {num_iters}")
+    ws = torch.empty(lib.ucn_colour_correct_ws_bytes(n), dtype=torch.uint8, device=dev)
+    out = torch.empty_like(p)
+    warps = torch.empty((num_iters, 10, 3), dtype=torch.float32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    _lib.check(lib.ucn_colour_correct(p.data_ptr(), g.data_ptr(), n, num_iters, float(eps), ws.data_ptr(), out.data_ptr(), warps.data_ptr(),
+                                      status.data_ptr(), _lib.stream()))
+    bits = int(status.item())                                 # the call's only synchronisation
+    if bits:
+        names = ", ".join(f"{c} ({'rgb'[c]})" for c in range(3) if bits >> c & 1)
+        raise RuntimeError(f"color_correct: the least-squares system of channel {names} is rank deficient (fewer than 10 independent "
+                           "unclipped pixels) or gave a non-finite warp")
+    return (out, warps) if return_warps else out
 
 
 class MetricHarness:
