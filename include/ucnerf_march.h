@@ -37,7 +37,9 @@ typedef void *ucn_stream_t; /* hipStream_t; NULL = the legacy default stream */
 
 /* ------------------------------------------------------------------ diagnostics */
 const char *ucn_last_error(void);
-/* ABI version: bump when a signature changes (checked by the Python loader). */
+/* ABI version: bump when a signature changes.  ucn_abi_version() returns the UCN_ABI_VERSION the library was built with; the Python
+ * loader, which binds every declaration of this file from its text, refuses a library that answers another number. */
+#define UCN_ABI_VERSION 32
 uint32_t ucn_abi_version(void);
 /* HBM bandwidth probe: device-to-device copy kernel, returns 0 and leaves timing to the caller. */
 int ucn_probe_copy(const float *src, float *dst, uint64_t n_floats, ucn_stream_t stream);

@@ -34,6 +34,11 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), f"{name} declared in include/ucnerf_march.h but not exported"
         assert name in _lib.SIGNATURES, f"{name} has no ctypes signature"
     assert lib.ucn_abi_version() == _lib.ABI_VERSION
+    # ... and the converse: an export the header does not declare is an entry point nothing binds and nothing tests
+    nm = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH], text=True)
+    exported = {line.split()[-1] for line in nm.splitlines() if line.split()[-1].startswith("ucn_")}
+    assert len(exported) >= 20
+    assert exported - declared == set(), "exported but not declared in include/ucnerf_march.h"
 
 
 def test_argument_errors_surface_as_messages_without_a_gpu():

@@ -46,9 +46,9 @@ def host_offsets(offsets):
 
 def _dtype_code(t):
     if t.dtype == torch.float32:
-        return 0
+        return _lib.DTYPE_F32
     if t.dtype == torch.float16:
-        return 1
+        return _lib.DTYPE_F16
     raise RuntimeError("embeddings must be float32 or float16 on this build (float64 tables are not supported)")
 
 

@@ -27,7 +27,7 @@ import torch
 
 from .. import _lib
 
-ACCUMULATE, RELU, MASK = 1, 2, 4
+ACCUMULATE, RELU, MASK = _lib.GEMM_ACCUMULATE, _lib.GEMM_RELU, _lib.GEMM_MASK
 
 H3_MIN_ROWS = 32768             # below this a GEMM is launch-bound either way (per-ray terms, the colour head): exact products, no pack
 _ENGINE = "exact" if os.environ.get("UCN_F32_EXACT", "0") == "1" else "split"

@@ -105,8 +105,8 @@ def _field_copy(desc, **members):
 
 # Model.raydist_fn -> the curve id of include/ucnerf_march.h (UCN_RAYDIST_*).  coord.py:151-172 selects a callable by its
 # __name__ and inverts it through `inv_mapping`; the gin-bound callables are configs.py:13-19's torch functions.
-RAYDIST_CURVES = {None: 0, 'piecewise': 1, 'power_transformation': 2}
-RAYDIST_TORCH = {'reciprocal': 3, 'log': 4, 'exp': 5, 'sqrt': 6, 'square': 7}
+RAYDIST_CURVES = {None: _lib.RAYDIST_IDENTITY, 'piecewise': _lib.RAYDIST_PIECEWISE, 'power_transformation': _lib.RAYDIST_POWER}
+RAYDIST_TORCH = {name: getattr(_lib, 'RAYDIST_' + name.upper()) for name in ('reciprocal', 'log', 'exp', 'sqrt', 'square')}
 
 
 def raydist_curve(fn):
