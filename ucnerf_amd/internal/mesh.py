@@ -36,8 +36,11 @@ def marching_cubes(volume, level=0.0, spacing=(1.0, 1.0, 1.0), allow_degenerate=
         _lib.check(lib.ucn_marching_cubes_emit(vol.data_ptr(), X, Y, Z, float(level), sx, sy, sz, ws.data_ptr(), verts.data_ptr(),
                                                _lib.ptr(normals), faces.data_ptr() if nt else None, st))
     if not allow_degenerate and nt:
-        # skimage's allow_degenerate=False: drop triangles of zero area (a vertex exactly on a lattice point collapses an edge)
+        # skimage's allow_degenerate=False: drop the triangles with two vertices at the same position (a value exactly at the
+        # level puts every vertex of the edges around it on that lattice point).  Decided on the coordinates, as skimage's
+        # remove_degenerate_faces does: a float32 cross product of two EQUAL edge vectors is only zero where the compiler
+        # does not fuse u_y w_z - u_z w_y into an fma, whose residual kept half of these faces at non-unit spacing
         a, b, c = (verts[faces[:, k].long()] for k in range(3))
-        keep = torch.linalg.cross(b - a, c - a).abs().sum(dim=-1) > 0
-        faces = faces[keep]
+        same = (a == b).all(dim=-1) | (b == c).all(dim=-1) | (a == c).all(dim=-1)
+        faces = faces[~same]
     return verts, faces, normals, None
