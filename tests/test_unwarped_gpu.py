@@ -45,6 +45,13 @@ def ray_args(fx, tdist, rand_vec, idx=None):
     return keep, [td.data_ptr(), None, None, o.data_ptr(), d.data_ptr(), basis.data_ptr(), rad.data_ptr(), None, None]
 
 
+def as_sdist(args, N):
+    """ray_args' pointer list read as NORMALISED fenceposts with near = 0 and far = 1 -- the kernels' TD = false instantiations, which
+    derive t = s * far + (1 - s) * near = s * 1 + (1 - s) * 0 = s exactly in float32: the same Gaussians as the metric ones, bit for bit."""
+    near, far = torch.zeros(N, device="cuda"), torch.ones(N, device="cuda")
+    return (near, far), [args[0], near.data_ptr(), far.data_ptr()] + args[3:]
+
+
 # ---------------------------------------------------------------------------------------------------- 1. cast probe
 def test_cast_probe_unwarped_vs_reference():
     """ucn_cast_probe_warp(warp = 0) against the reference's render.cast_rays: the bars of
@@ -68,6 +75,12 @@ def test_cast_probe_unwarped_vs_reference():
     assert torch.equal(got[..., 5:8][ok], got[..., 0:3][ok]) and torch.equal(got[..., 8][ok], got[..., 3][ok])
     _, rs = U.grid_inputs(means, stds)
     assert float(((got[..., 9] - rs).abs() / rs)[ok].max()) <= 2e-5
+    # k_cast_probe<TD = false, WARP = false>: the same fenceposts as normalised ones of near = 0, far = 1
+    keep2, args_sd = as_sdist(args, N)
+    out_sd = torch.full((N, S, 6, 10), float("nan"), device="cuda")
+    _lib.check(lib.ucn_cast_probe_warp(*args_sd, 0.5, 0, N, S, out_sd.data_ptr(), _lib.stream()))
+    torch.cuda.synchronize()
+    assert torch.equal(out_sd.cpu().view(torch.int32), out.cpu().view(torch.int32))
 
 
 # ---------------------------------------------------------------------------------------------------- 2. eval forward
@@ -286,6 +299,30 @@ def test_unwarped_normals_and_outside_normals_are_minus_zero():
     assert float((nrm[inside].norm(dim=-1) - 1).abs().median()) <= 1e-5           # unit vectors where the grid has a gradient
     dens = h["density"].cpu().reshape(out_mask.shape)
     assert float(dens[out_mask].max() - dens[out_mask].min()) == 0.0              # zero grid features: one density outside the cube
+    # the model above marches normalised fenceposts (k_march_density_grad<C, TD = false, WARP = false>); the metric ones (TD = true) on
+    # the entry point itself: the march's fenceposts as metric ones against the same as normalised ones of near = 0, far = 1, bit for bit
+    from ucnerf_amd import _lib
+    lib = _lib.load()
+    mlp = model.nerf_mlp
+    N, S = out_mask.shape
+    sd = h["sdist"].reshape(N, -1).cpu()
+    keep, args = ray_args(fx, sd * fx["ray_far"] + (1 - sd) * fx["ray_near"], fx["noise1_rand_vec"].reshape(N, -1))
+    keep_sd, args_sd = as_sdist(args, N)
+    L, C = mlp.encoder.num_levels, mlp.encoder.level_dim
+    gfeat = torch.randn(L, N * S, C, generator=torch.Generator().manual_seed(3)).cuda()
+    d = mlp.grid_field()
+    got = []
+    for a in (args, args_sd):
+        rg, nr = torch.full((N * S, 3), float("nan"), device="cuda"), torch.full((N * S, 3), float("nan"), device="cuda")
+        _lib.check(lib.ucn_march_density_grad_warp(ctypes.byref(d), *a, 0.5, 0, N, S, 0, gfeat.data_ptr(), rg.data_ptr(), nr.data_ptr(),
+                                                   _lib.stream()))
+        torch.cuda.synchronize()
+        got.append((rg.cpu(), nr.cpu()))
+    assert bool(torch.isfinite(got[0][0]).all()) and float(got[0][0].abs().max()) > 0
+    assert torch.equal(got[0][0].view(torch.int32), got[1][0].view(torch.int32))
+    assert torch.equal(got[0][1].view(torch.int32), got[1][1].view(torch.int32))
+    om = out_mask.reshape(-1)
+    assert torch.equal(got[0][0][om], torch.zeros_like(got[0][0][om])) and bool(torch.signbit(got[0][1][om]).all())
 
 
 # ---------------------------------------------------------------------------------------------------- 6. refusals

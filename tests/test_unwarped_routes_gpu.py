@@ -16,7 +16,7 @@ from oracle import raymarch as rm
 from oracle import truth64 as t64
 from test_glo_gpu import types_ns
 from test_unwarped_cpu import sub
-from test_unwarped_gpu import fixture, outside_samples, ray_args, unwarped_model
+from test_unwarped_gpu import as_sdist, fixture, outside_samples, ray_args, unwarped_model
 
 pytestmark = pytest.mark.gpu
 
@@ -139,9 +139,10 @@ def test_unwarped_renderings_bracket_every_level(run):
 
 
 def test_unwarped_table_gradient_bracket():
-    """Part 1 of test_table_gradient_bracket_full_size on the unwarped field (float rows, the row-block route and the atomic one):
-    per level, the relative L2 distance of the table gradient of a random upstream gradient to float64 autograd, against the
-    float32 oracle's own."""
+    """Part 1 of test_table_gradient_bracket_full_size on the unwarped field (float rows; the compacted row-block route, the plain
+    row-block kernel re-deriving its own geometry -- levels_per_block 0 without a workspace -- and the atomic one; each on metric
+    fenceposts, TD = true, and on the same fenceposts as normalised ones of near = 0 and far = 1, TD = false): per level, the
+    relative L2 distance of the table gradient of a random upstream gradient to float64 autograd, against the float32 oracle's own."""
     from ucnerf_amd import _lib
     lib = _lib.load()
     fx = fixture("rand_")
@@ -170,17 +171,18 @@ def test_unwarped_table_gradient_bracket():
     g = grad.reshape(N * S, L * C).cuda().contiguous()
     _, offsets, grid_sizes, _ = fs.layout()
     off = [int(o) for o in offsets]
-    for lpb, with_ws in ((0, True), (1, False)):
+    keep_sd, args_sd = as_sdist(args, N)
+    for lpb, with_ws, td in ((0, True, True), (0, False, True), (1, False, True), (0, True, False), (0, False, False), (1, False, False)):
         gt = torch.zeros_like(mlp.encoder.embeddings.detach())
         ws = torch.empty(lib.ucn_march_features_backward_ws_floats(ctypes.byref(d), N, S), device="cuda") if with_ws else None
-        _lib.check(lib.ucn_march_features_backward_warp(ctypes.byref(d), *args, 0.5, 0, N, S, lpb, 1, g.data_ptr(), gt.data_ptr(),
-                                                        _lib.ptr(ws), _lib.stream()))
+        _lib.check(lib.ucn_march_features_backward_warp(ctypes.byref(d), *(args if td else args_sd), 0.5, 0, N, S, lpb, 1, g.data_ptr(),
+                                                        gt.data_ptr(), _lib.ptr(ws), _lib.stream()))
         torch.cuda.synchronize()
         hip = gt.double().cpu()
         for l in range(L):
             a, b, c = (x[off[l]:off[l + 1]] for x in (hip, emb.grad.double(), table.grad))
-            H.bracket(f"unwarped table gradient lpb {lpb} level {l} (side {int(grid_sizes[l])}) rel L2", [float((b - c).norm() / c.norm())],
-                      [float((a - c).norm() / c.norm())], K, floor=(1e-6, 1e-6))
+            H.bracket(f"unwarped table gradient lpb {lpb} workspace {with_ws} metric {td} level {l} (side {int(grid_sizes[l])}) rel L2",
+                      [float((b - c).norm() / c.norm())], [float((a - c).norm() / c.norm())], K, floor=(1e-6, 1e-6))
 
 
 # ---------------------------------------------------------------------------------------------------- 2. density normals

@@ -90,7 +90,8 @@ UCN_SAME_IN_EVERY_UNIT __device__ __forceinline__ void contract_to_unit(float x,
 // 6x4 floats per sample).  TD: in.sdist holds metric fenceposts (see RayInputs).
 // WARP = false (MLP.warp_fn = None, a bounded scene): the Gaussians reach the grid as cast, u = (x + 1) / 2 and std unscaled.
 // A template argument, not a run-time one: with WARP = true the body is the one every kernel inlined before the argument
-// existed, so those kernels keep their machine code (profiles/unwarped/isa_identity.txt).
+// existed, so those kernels keep their machine code (profiles/unwarped/isa_identity.txt).  A kernel that calls this hands on a
+// trailing `bool WARP = true` of its own: one __global__ text per kernel, no *_body twin and no k_*_unwarped sibling.
 template <bool TD = false, bool WARP = true>
 UCN_SAME_IN_EVERY_UNIT __device__ __forceinline__ void cast_sample(const RayInputs &in, const HexPattern &hx, float std_scale, uint32_t ray,
                                             uint32_t s, uint32_t S, float (&u)[6][3], float (&rs)[6],

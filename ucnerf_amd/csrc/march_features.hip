@@ -350,26 +350,16 @@ __device__ __forceinline__ void featurise(const UcnLevels &lvls, const TT *__res
 
 // Introspection for the parity tests: the product's own cast_sample / contract_to_unit, results
 // written out instead of consumed.
-template <bool TD, bool WARP>
-__device__ __forceinline__ void cast_probe_body(const RayInputs &in, const HexPattern &hx, float std_scale, uint32_t N, uint32_t S,
-                                                float *__restrict__ out) {
+// WARP = false (MLP.warp_fn = None): floats 5..8 of a point repeat its cast mean and std, 9 is 1 / sqrt(8 std^2) of the uncontracted std
+template <bool TD = false, bool WARP = true>
+__global__ __launch_bounds__(256) void k_cast_probe(RayInputs in, HexPattern hx, float std_scale, uint32_t N, uint32_t S,
+                                                    float *__restrict__ out) {
     const size_t B = (size_t)N * S;
     const size_t b = (size_t)blockIdx.x * 256u + threadIdx.x;
     if (b >= B) return;
     const uint32_t ray = (uint32_t)(b / S), s = (uint32_t)(b - (size_t)ray * S);
     float u[6][3], rs[6], csum[3], tsum;
     cast_sample<TD, WARP>(in, hx, std_scale, ray, s, S, u, rs, csum, tsum, out + b * 6 * UCN_CAST_PROBE_FLOATS);
-}
-template <bool TD = false>
-__global__ __launch_bounds__(256) void k_cast_probe(RayInputs in, HexPattern hx, float std_scale, uint32_t N, uint32_t S,
-                                                    float *__restrict__ out) {
-    cast_probe_body<TD, true>(in, hx, std_scale, N, S, out);
-}
-// MLP.warp_fn = None: floats 5..8 of a point repeat its cast mean and std, 9 is 1 / sqrt(8 std^2) of the uncontracted std
-template <bool TD = false>
-__global__ __launch_bounds__(256) void k_cast_probe_unwarped(RayInputs in, HexPattern hx, float std_scale, uint32_t N, uint32_t S,
-                                                             float *__restrict__ out) {
-    cast_probe_body<TD, false>(in, hx, std_scale, N, S, out);
 }
 
 __global__ __launch_bounds__(256) void k_contract_probe(const float *__restrict__ means, const float *__restrict__ stds,
@@ -545,10 +535,10 @@ __global__ __launch_bounds__(256) void k_points_features(UcnLevels lvls, const f
 
 }  // namespace
 
-template <bool TD>
+template <bool TD, bool WARP>
 static int march_features_launch(const ucn_field_t *f, const RayInputs &in, float std_scale, uint32_t N, uint32_t S,
                                  uint32_t levels_per_block, int layout, float *features_out, float *coord_out, float *tmean_out,
-                                 ucn_stream_t stream, bool warp = true) {
+                                 ucn_stream_t stream) {
     UCN_REQUIRE(N == 0 || (in.sdist && (TD || (in.near_ && in.far_)) && in.origins && in.dirs && in.basis && in.radii && features_out),
                 "march_features: null pointer argument");
     UCN_REQUIRE((in.flip == nullptr) == (in.spin == nullptr), "march_features: flip and spin come together");
@@ -577,35 +567,23 @@ static int march_features_launch(const ucn_field_t *f, const RayInputs &in, floa
     const uint32_t tpb = coresident ? 512u : 256u;
     const size_t lds = coresident ? 88u * 1024u : 0u;
     const dim3 grid(ucn_div_up(B, tpb), grp.n);
-#define UCN_MF3(KF, CC, FEW)                                                                                                  \
+// UCN_MF3(kernel, C, trailing template arguments ...): the three launch shapes of one gather kernel
+#define UCN_MF3(KF, CC, ...)                                                                                              \
     do {                                                                                                                  \
         if (half_table)                                                                                                   \
-            hipLaunchKernelGGL((KF<CC, 256, _Float16, FEW>), grid, dim3(256), lds, st, lv,                  \
+            hipLaunchKernelGGL((KF<CC, 256, _Float16, __VA_ARGS__>), grid, dim3(256), lds, st, lv,                        \
                                reinterpret_cast<const _Float16 *>(f->embeddings), in, hx, std_scale, N, S, grp, layout,   \
                                features_out, coord_out, tmean_out);                                                       \
         else if (coresident)                                                                                              \
-            hipLaunchKernelGGL((KF<CC, 512, float, FEW>), grid, dim3(512), lds, st, lv, f->embeddings, in, hx, std_scale, N, S, \
-                               grp, layout, features_out, coord_out, tmean_out);                                          \
+            hipLaunchKernelGGL((KF<CC, 512, float, __VA_ARGS__>), grid, dim3(512), lds, st, lv, f->embeddings, in, hx,    \
+                               std_scale, N, S, grp, layout, features_out, coord_out, tmean_out);                         \
         else                                                                                                              \
-            hipLaunchKernelGGL((KF<CC, 256, float, FEW>), grid, dim3(256), lds, st, lv, f->embeddings, in, hx, std_scale, N, S, \
-                               grp, layout, features_out, coord_out, tmean_out);                                          \
-    } while (0)
-#define UCN_MF3U(CC, FEW)                                                                                                 \
-    do {                                                                                                                  \
-        if (half_table)                                                                                                   \
-            hipLaunchKernelGGL((k_march_features_unwarped<CC, 256, _Float16, TD, FEW>), grid, dim3(256), lds, st, lv,         \
-                               reinterpret_cast<const _Float16 *>(f->embeddings), in, hx, std_scale, N, S, grp, layout,   \
-                               features_out, coord_out, tmean_out);                                                       \
-        else if (coresident)                                                                                              \
-            hipLaunchKernelGGL((k_march_features_unwarped<CC, 512, float, TD, FEW>), grid, dim3(512), lds, st, lv, f->embeddings, in, \
-                               hx, std_scale, N, S, grp, layout, features_out, coord_out, tmean_out);                       \
-        else                                                                                                              \
-            hipLaunchKernelGGL((k_march_features_unwarped<CC, 256, float, TD, FEW>), grid, dim3(256), lds, st, lv, f->embeddings, in, \
-                               hx, std_scale, N, S, grp, layout, features_out, coord_out, tmean_out);                       \
+            hipLaunchKernelGGL((KF<CC, 256, float, __VA_ARGS__>), grid, dim3(256), lds, st, lv, f->embeddings, in, hx,    \
+                               std_scale, N, S, grp, layout, features_out, coord_out, tmean_out);                         \
     } while (0)
 #define UCN_MF2(CC, FEW)                                                                                                  \
     do {                                                                                                                  \
-        if (!warp) UCN_MF3U(CC, FEW);                                                                                     \
+        if constexpr (!WARP) UCN_MF3(k_march_features_unwarped, CC, TD, FEW);                                             \
         else if constexpr (TD) UCN_MF3(k_march_features_td, CC, FEW);                                                     \
         else UCN_MF3(k_march_features, CC, FEW);                                                                          \
     } while (0)
@@ -615,7 +593,6 @@ static int march_features_launch(const ucn_field_t *f, const RayInputs &in, floa
         else UCN_MF2(CC, false);
     });
 #undef UCN_MF3
-#undef UCN_MF3U
 #undef UCN_MF2
     UCN_LAUNCH_CHECK("march_features");
     return 0;
@@ -629,11 +606,14 @@ extern "C" int ucn_march_features_warp(const ucn_field_t *f, const float *fencep
     UCN_REQUIRE(warp == 0 || warp == 1, "march_features: warp must be 0 (MLP.warp_fn = None) or 1 ('contract'), got %d", warp);
     UCN_REQUIRE(N == 0 || (near_ == nullptr) == (far_ == nullptr), "march_features: near and far come together (both NULL: metric fenceposts)");
     const RayInputs in{fenceposts, near_, far_, origins, directions, basis, radii, flip, spin};
-    if (near_ == nullptr)
-        return march_features_launch<true>(f, in, std_scale, N, S, levels_per_block, layout, features_out, coord_out, tmean_out,
-                                           stream, warp != 0);
-    return march_features_launch<false>(f, in, std_scale, N, S, levels_per_block, layout, features_out, coord_out, tmean_out,
-                                        stream, warp != 0);
+    int rc = 0;
+    ucn_for_bool(near_ == nullptr, [&](auto td) {
+        ucn_for_bool(warp != 0, [&](auto w) {
+            rc = march_features_launch<decltype(td)::value, decltype(w)::value>(f, in, std_scale, N, S, levels_per_block, layout,
+                                                                                features_out, coord_out, tmean_out, stream);
+        });
+    });
+    return rc;
 }
 
 extern "C" int ucn_march_features(const ucn_field_t *f, const float *sdist, const float *near_, const float *far_,
@@ -655,19 +635,14 @@ extern "C" int ucn_march_features_tdist(const ucn_field_t *f, const float *tdist
                                    levels_per_block, layout, features_out, coord_out, tmean_out, stream);
 }
 
-template <bool TD>
-static int cast_probe_launch(const RayInputs &in, float std_scale, uint32_t N, uint32_t S, float *out, ucn_stream_t stream,
-                             bool warp = true) {
+template <bool TD, bool WARP>
+static int cast_probe_launch(const RayInputs &in, float std_scale, uint32_t N, uint32_t S, float *out, ucn_stream_t stream) {
     UCN_REQUIRE(N == 0 || (in.sdist && (TD || (in.near_ && in.far_)) && in.origins && in.dirs && in.basis && in.radii && out),
                 "cast_probe: null pointer argument");
     UCN_REQUIRE((in.flip == nullptr) == (in.spin == nullptr), "cast_probe: flip and spin come together");
     if (N == 0 || S == 0) return 0;
-    if (warp)
-        hipLaunchKernelGGL(k_cast_probe<TD>, dim3(ucn_div_up((size_t)N * S, 256)), dim3(256), 0, (hipStream_t)stream, in, make_hex(),
-                           std_scale, N, S, out);
-    else
-        hipLaunchKernelGGL(k_cast_probe_unwarped<TD>, dim3(ucn_div_up((size_t)N * S, 256)), dim3(256), 0, (hipStream_t)stream, in,
-                           make_hex(), std_scale, N, S, out);
+    hipLaunchKernelGGL((k_cast_probe<TD, WARP>), dim3(ucn_div_up((size_t)N * S, 256)), dim3(256), 0, (hipStream_t)stream, in, make_hex(),
+                       std_scale, N, S, out);
     UCN_LAUNCH_CHECK("cast_probe");
     return 0;
 }
@@ -679,8 +654,11 @@ extern "C" int ucn_cast_probe_warp(const float *fenceposts, const float *near_, 
     UCN_REQUIRE(warp == 0 || warp == 1, "cast_probe: warp must be 0 (MLP.warp_fn = None) or 1 ('contract'), got %d", warp);
     UCN_REQUIRE(N == 0 || (near_ == nullptr) == (far_ == nullptr), "cast_probe: near and far come together (both NULL: metric fenceposts)");
     const RayInputs in{fenceposts, near_, far_, origins, directions, basis, radii, flip, spin};
-    if (near_ == nullptr) return cast_probe_launch<true>(in, std_scale, N, S, out, stream, warp != 0);
-    return cast_probe_launch<false>(in, std_scale, N, S, out, stream, warp != 0);
+    int rc = 0;
+    ucn_for_bool(near_ == nullptr, [&](auto td) {
+        ucn_for_bool(warp != 0, [&](auto w) { rc = cast_probe_launch<decltype(td)::value, decltype(w)::value>(in, std_scale, N, S, out, stream); });
+    });
+    return rc;
 }
 
 extern "C" int ucn_cast_probe(const float *sdist, const float *near_, const float *far_, const float *origins,

@@ -284,27 +284,9 @@ __device__ __forceinline__ void featurise_bwd(const UcnLevels &lvls, float *__re
 // @torch.no_grad, coord.py:75, and sdist is detached, models.py:204-205.)  fp32 atomics in L2, like
 // kernel_grid_backward (gridencoder.cu:336).
 //
-// Every kernel below that re-derives the Gaussians exists twice: the warped one under the name and with the text it always had, and
-// k_*_unwarped (MLP.warp_fn = None) around a body template that repeats that text with the warp as a compile-time argument.  Two
-// texts on purpose: with the warped kernel as a call of the shared body its machine code came out in another schedule (1 to 36
-// instructions of 1 000 to 22 000, profiles/unwarped/isa_identity.txt), and the shipped kernels are to stay byte-identical.  A
-// change to one text belongs in the other.  The kernels that read the geometry cache (k_march_features_bwd_cmp, the cached route of *_blk) need neither:
-// a point outside the unit cube is skipped by in_unit_cube in every scatter and has no bit in the block masks.
-template <uint32_t C, bool TD, bool WARP>
-__device__ __forceinline__ void march_features_bwd_body(const UcnLevels &lvls, float *__restrict__ grad_table, const RayInputs &in,
-                                                        const HexPattern &hx, float std_scale, uint32_t N, uint32_t S,
-                                                        uint32_t lpb, int layout, const float *__restrict__ grad_features) {
-    const size_t B = (size_t)N * S;
-    const size_t b = (size_t)blockIdx.x * 256u + threadIdx.x;
-    if (b >= B) return;
-    const uint32_t ray = (uint32_t)(b / S), s = (uint32_t)(b - (size_t)ray * S);
-    float u[6][3], rs[6], csum[3], tsum;
-    cast_sample<TD, WARP>(in, hx, std_scale, ray, s, S, u, rs, csum, tsum);
-    const uint32_t lvl0 = blockIdx.y * lpb;
-    const uint32_t lvl1 = lvl0 + lpb < lvls.L ? lvl0 + lpb : lvls.L;
-    featurise_bwd<C>(lvls, grad_table, lvl0, lvl1, u, rs, 6, B, b, grad_features, layout == 1);
-}
-template <uint32_t C, bool TD = false>
+// WARP (every kernel below that re-derives the Gaussians): cast_sample<TD, WARP>, false = MLP.warp_fn = None, the Gaussians as cast.
+// The kernels that read the geometry cache (k_march_features_bwd_cmp, the cached route of *_blk) need neither TD nor WARP.
+template <uint32_t C, bool TD = false, bool WARP = true>
 __global__ __launch_bounds__(256) void k_march_features_bwd(UcnLevels lvls, float *__restrict__ grad_table, RayInputs in,
                                                             HexPattern hx, float std_scale, uint32_t N, uint32_t S,
                                                             uint32_t lpb, int layout,
@@ -314,17 +296,10 @@ __global__ __launch_bounds__(256) void k_march_features_bwd(UcnLevels lvls, floa
     if (b >= B) return;
     const uint32_t ray = (uint32_t)(b / S), s = (uint32_t)(b - (size_t)ray * S);
     float u[6][3], rs[6], csum[3], tsum;
-    cast_sample<TD>(in, hx, std_scale, ray, s, S, u, rs, csum, tsum);
+    cast_sample<TD, WARP>(in, hx, std_scale, ray, s, S, u, rs, csum, tsum);
     const uint32_t lvl0 = blockIdx.y * lpb;
     const uint32_t lvl1 = lvl0 + lpb < lvls.L ? lvl0 + lpb : lvls.L;
     featurise_bwd<C>(lvls, grad_table, lvl0, lvl1, u, rs, 6, B, b, grad_features, layout == 1);
-}
-template <uint32_t C, bool TD = false>
-__global__ __launch_bounds__(256) void k_march_features_bwd_unwarped(UcnLevels lvls, float *__restrict__ grad_table, RayInputs in,
-                                                                     HexPattern hx, float std_scale, uint32_t N, uint32_t S,
-                                                                     uint32_t lpb, int layout,
-                                                                     const float *__restrict__ grad_features) {
-    march_features_bwd_body<C, TD, false>(lvls, grad_table, in, hx, std_scale, N, S, lpb, layout, grad_features);
 }
 
 // Same gradient without global atomics.  Scattered fp32 atomics run at ~21 G/s on MI355X whatever their
@@ -337,9 +312,9 @@ __global__ __launch_bounds__(256) void k_march_features_bwd_unwarped(UcnLevels l
 // The six contracted multisample positions and damping arguments of every sample, as [N*S][6] float4
 // {x, y, z, std argument} (one 16-byte load per point for the compacted kernel's scattered items): written once
 // per backward call, read by every (level, row block) workgroup.
-template <bool TD, bool WARP>
-__device__ __forceinline__ void cast_cache_body(const RayInputs &in, const HexPattern &hx, float std_scale, uint32_t N, uint32_t S,
-                                                float *__restrict__ geom) {
+template <bool TD = false, bool WARP = true>
+__global__ __launch_bounds__(256) void k_cast_cache(RayInputs in, HexPattern hx, float std_scale, uint32_t N, uint32_t S,
+                                                    float *__restrict__ geom) {
     const size_t B = (size_t)N * S;
     const size_t b = (size_t)blockIdx.x * 256u + threadIdx.x;
     if (b >= B) return;
@@ -350,25 +325,6 @@ __device__ __forceinline__ void cast_cache_body(const RayInputs &in, const HexPa
     for (uint32_t j = 0; j < 6; j++) {
         reinterpret_cast<float4 *>(geom)[b * 6 + j] = make_float4(u[j][0], u[j][1], u[j][2], rs[j]);
     }
-}
-template <bool TD = false>
-__global__ __launch_bounds__(256) void k_cast_cache(RayInputs in, HexPattern hx, float std_scale, uint32_t N, uint32_t S,
-                                                    float *__restrict__ geom) {
-    const size_t B = (size_t)N * S;
-    const size_t b = (size_t)blockIdx.x * 256u + threadIdx.x;
-    if (b >= B) return;
-    const uint32_t ray = (uint32_t)(b / S), s = (uint32_t)(b - (size_t)ray * S);
-    float u[6][3], rs[6], csum[3], tsum;
-    cast_sample<TD>(in, hx, std_scale, ray, s, S, u, rs, csum, tsum);
-#pragma unroll
-    for (uint32_t j = 0; j < 6; j++) {
-        reinterpret_cast<float4 *>(geom)[b * 6 + j] = make_float4(u[j][0], u[j][1], u[j][2], rs[j]);
-    }
-}
-template <bool TD = false>
-__global__ __launch_bounds__(256) void k_cast_cache_unwarped(RayInputs in, HexPattern hx, float std_scale, uint32_t N, uint32_t S,
-                                                             float *__restrict__ geom) {
-    cast_cache_body<TD, false>(in, hx, std_scale, N, S, geom);
 }
 
 // ---- block masks: which row blocks of a level a sample touches.  Planes of [N*S] uint32 behind the geometry
@@ -514,14 +470,14 @@ __device__ __forceinline__ uint32_t point_block_mask(const UcnLevel &lv, uint32_
 }
 
 // geometry planes + block masks of every sample, once per backward call
-template <bool TD, bool WARP>
-__device__ __forceinline__ void cast_cache_masks_body(const UcnLevels &lvls, const RayInputs &in, const HexPattern &hx, float std_scale,
-                                                      uint32_t N, uint32_t S, const MaskPlan &plan,
-                                                      const float *__restrict__ grad_features, const GradStrides &gs, uint32_t C,
-                                                      float *__restrict__ geom, uint32_t *__restrict__ masks,
-                                                      float *__restrict__ grad_level_major /*[L][N*S][C], / 6*/,
-                                                      uint32_t *__restrict__ task_counter,
-                                                      float *__restrict__ l1_partial /*[L][gridDim.x] or null: sum over the block's samples of max_c |g|*/) {
+template <bool TD = false, bool WARP = true>
+__global__ __launch_bounds__(256, 1) void k_cast_cache_masks(UcnLevels lvls, RayInputs in, HexPattern hx, float std_scale,
+                                                          uint32_t N, uint32_t S, MaskPlan plan,
+                                                          const float *__restrict__ grad_features, GradStrides gs, uint32_t C,
+                                                          float *__restrict__ geom, uint32_t *__restrict__ masks,
+                                                          float *__restrict__ grad_level_major /*[L][N*S][C], / 6*/,
+                                                          uint32_t *__restrict__ task_counter,
+                                                          float *__restrict__ l1_partial /*[L][gridDim.x] or null: sum over the block's samples of max_c |g|*/) {
     const size_t B = (size_t)N * S;
     const size_t b = (size_t)blockIdx.x * 256u + threadIdx.x;
     if (b < 8) task_counter[b] = 0u;                      // the compacted kernel's persistent workgroups pull tasks from here
@@ -668,170 +624,6 @@ __device__ __forceinline__ void cast_cache_masks_body(const UcnLevels &lvls, con
                 ((s_l1[threadIdx.x][0] + s_l1[threadIdx.x][1]) + s_l1[threadIdx.x][2]) + s_l1[threadIdx.x][3];
     }
 }
-template <bool TD = false>
-__global__ __launch_bounds__(256, 1) void k_cast_cache_masks(UcnLevels lvls, RayInputs in, HexPattern hx, float std_scale,
-                                                          uint32_t N, uint32_t S, MaskPlan plan,
-                                                          const float *__restrict__ grad_features, GradStrides gs, uint32_t C,
-                                                          float *__restrict__ geom, uint32_t *__restrict__ masks,
-                                                          float *__restrict__ grad_level_major /*[L][N*S][C], / 6*/,
-                                                          uint32_t *__restrict__ task_counter,
-                                                          float *__restrict__ l1_partial /*[L][gridDim.x] or null: sum over the block's samples of max_c |g|*/) {
-    const size_t B = (size_t)N * S;
-    const size_t b = (size_t)blockIdx.x * 256u + threadIdx.x;
-    if (b < 8) task_counter[b] = 0u;                      // the compacted kernel's persistent workgroups pull tasks from here
-    __shared__ float s_l1[UCN_MAX_LEVELS][4];             // per level: the four waves' sums of max_c |g| (fixed-point bound)
-    if ((threadIdx.x & 63u) < UCN_MAX_LEVELS) s_l1[threadIdx.x & 63u][threadIdx.x >> 6] = 0.0f;   // own column (a wave past the end leaves zeros)
-    // whole waves only (the bit planes below are built by wave ballots); a wave past the end skips the body but still reaches the
-    // barrier of the l1_partial reduction at the bottom (an early `return` left the barrier to part of the workgroup)
-    const bool live_wave = (b & ~(size_t)63) < B;
-    do {
-    if (!live_wave) break;
-    const bool valid = b < B;
-    const size_t bb = valid ? b : B - 1;                  // lanes past the end recompute the last sample and store nothing
-    const uint32_t ray = (uint32_t)(bb / S), s = (uint32_t)(bb - (size_t)ray * S);
-    float u[6][3], rs[6], csum[3], tsum;
-    cast_sample<TD>(in, hx, std_scale, ray, s, S, u, rs, csum, tsum);
-    if (valid) {
-#pragma unroll
-        for (uint32_t j = 0; j < 6; j++) {
-            reinterpret_cast<float4 *>(geom)[b * 6 + j] = make_float4(u[j][0], u[j][1], u[j][2], rs[j]);
-        }
-    }
-    __shared__ uint32_t s_words[kMaxMaskWords * 256u];    // [word][thread]: a thread's own column, bank = thread
-    for (uint32_t lvl = 0; lvl < lvls.L; lvl++) {
-        const UcnLevel lv = lvls.lv[lvl];
-        const uint32_t nb_l = (lv.rows + (1u << plan.shift) - 1u) >> plan.shift;
-        bool nz = false;
-        float gmax = 0.0f;
-        for (uint32_t c = 0; c < C; c++) {
-            const float g = grad_features[lvl * gs.level + bb * gs.sample + c * gs.chan];
-            nz |= valid && g != 0.0f;
-            gmax = fmaxf(gmax, valid ? fabsf(g) : 0.0f);
-            if (valid && !(fabsf(g) <= 3.0e38f)) gmax = __builtin_inff();        // NaN / inf poisons the bound (fmaxf drops NaN)
-            // the row-block workgroups fetch gradients per ITEM (scattered): give them 8 contiguous bytes per sample,
-            // already divided by the 6 multisamples of the mean (an IEEE division is ~13 VALU instructions per channel;
-            // an item stage would repeat it ~27 times per sample and level)
-            if (valid && grad_level_major) grad_level_major[((size_t)lvl * B + b) * C + c] = g / 6.0f;
-        }
-        if (!grad_level_major) gmax *= 6.0f;                // layout 4: g arrived divided by 6 -- the bound is on the undivided gradient (6 addends of <= |g| / 6 x w)
-        if (l1_partial) {                                   // (workgroup-uniform; every wave of the block gets here: no early `continue` above)
-            const float wsum = wave_sum_dpp<float>(gmax);
-            if ((threadIdx.x & 63u) == 0u) s_l1[lvl][threadIdx.x >> 6] = wsum;
-        }
-        if (nb_l > 32u || plan.coarse[lvl] == 3) {
-            // one bit per (sample, block) in nb / 32 words: set through the thread's own LDS column (dynamic word index)
-            const uint32_t nw = (nb_l + 31u) / 32u;
-            for (uint32_t k = 0; k < nw; k++) s_words[k * 256u + threadIdx.x] = 0u;
-            if (nz) {
-#pragma unroll
-                for (uint32_t j = 0; j < 6; j++) {
-                    if (!in_unit_cube(u[j][0], u[j][1], u[j][2])) continue;
-                    float fx, fy, fz;
-                    uint32_t rows[8];
-                    if (lv.hashed) { if (lv.mask) corner_rows<true, true>(lv, u[j][0], u[j][1], u[j][2], fx, fy, fz, rows); else corner_rows<true, false>(lv, u[j][0], u[j][1], u[j][2], fx, fy, fz, rows); }
-                    else { if (lv.mask) corner_rows<false, true>(lv, u[j][0], u[j][1], u[j][2], fx, fy, fz, rows); else corner_rows<false, false>(lv, u[j][0], u[j][1], u[j][2], fx, fy, fz, rows); }
-#pragma unroll
-                    for (uint32_t k = 0; k < 8; k++) {
-                        const uint32_t blk = rows[k] >> plan.shift;
-                        atomicOr(&s_words[(blk >> 5) * 256u + threadIdx.x], 1u << (blk & 31u));     // ds_or_b32, own column
-                    }
-                }
-            }
-            if (plan.coarse[lvl] == 3) {
-                // wide_block's layout: BIT PLANES [block][ceil(B / 64)] x 64 bits, one bit per sample -- the scanning workgroup of
-                // a block then reads B / 8 bytes instead of 4 B (measured in place with phase clocks: the word-per-sample scan
-                // was HALF of such a workgroup's time, one exposed load latency per 4096 samples).  A wave = 64 consecutive
-                // samples: 32 ballots per mask word, lane i keeps the ballot of block 32 w + i.
-                const uint32_t lane = threadIdx.x & 63u;
-                const size_t B64 = (B + 63u) / 64u, wave_global = b >> 6;
-                uint32_t *T = masks + (size_t)plan.plane[lvl] * B;
-                for (uint32_t w = 0; w < nw; w++) {
-                    const uint32_t word = s_words[w * 256u + threadIdx.x];
-                    uint32_t keep_lo = 0u, keep_hi = 0u;
-#pragma unroll
-                    for (uint32_t bit = 0; bit < 32u; bit++) {
-                        const uint64_t bal = __ballot((word >> bit) & 1u);
-                        if (lane == bit) { keep_lo = (uint32_t)bal; keep_hi = (uint32_t)(bal >> 32); }
-                    }
-                    const uint32_t blk = w * 32u + lane;
-                    if (lane < 32u && blk < nb_l) {
-                        T[((size_t)blk * B64 + wave_global) * 2u] = keep_lo;
-                        T[((size_t)blk * B64 + wave_global) * 2u + 1u] = keep_hi;
-                    }
-                }
-                continue;
-            }
-            if (valid) {
-                uint32_t *mpw = masks + (size_t)plan.plane[lvl] * B + b;
-                for (uint32_t k = 0; k < nw; k++) mpw[(size_t)k * B] = s_words[k * 256u + threadIdx.x];
-            }
-            continue;
-        }
-        uint32_t m[6];
-#pragma unroll
-        for (uint32_t j = 0; j < 6; j++) {
-            if (lv.hashed) m[j] = lv.mask ? point_block_mask<true, true>(lv, plan.shift, u[j]) : point_block_mask<true, false>(lv, plan.shift, u[j]);
-            else m[j] = lv.mask ? point_block_mask<false, true>(lv, plan.shift, u[j]) : point_block_mask<false, false>(lv, plan.shift, u[j]);
-        }
-        // a sample whose feature gradient on this level is exactly zero contributes nothing: clear its masks here
-        // so that the scanning workgroups never have to look at the gradient
-        if (!nz) {
-#pragma unroll
-            for (uint32_t j = 0; j < 6; j++) m[j] = 0u;
-        }
-        if (plan.fine_kind[lvl] == 3) {
-            // BYTE PLANES (cmp_block_bytes): plane p = B bytes, byte b = the six point bits of sample b for row block p.  A thread
-            // spreads its masks into words of four block bytes (nibble x 0x00204081 puts bit i of a nibble at bit 8 i), the four
-            // threads of a quad (samples 4 q ... 4 q + 3; B % 4 == 0, so a quad is in range or not as a whole) transpose 4 x 4 bytes
-            // through DPP quad broadcasts + v_perm_b32, and thread i of the quad stores the dword of block 4 k + i.
-            const uint32_t qi = threadIdx.x & 3u;
-            const uint32_t sel01 = qi | ((4u + qi) << 8) | 0x0c0c0000u, sel23 = 0x00000c0cu | (qi << 16) | ((4u + qi) << 24);
-            uint8_t *pl = reinterpret_cast<uint8_t *>(masks + (size_t)plan.plane[lvl] * B);
-            const uint32_t groups = (nb_l + 3u) / 4u;
-            for (uint32_t k = 0; k < groups; k++) {
-                uint32_t wk = 0u;
-#pragma unroll
-                for (uint32_t j = 0; j < 6; j++) wk |= ((((m[j] >> (4u * k)) & 15u) * 0x00204081u) & 0x01010101u) << j;
-                const uint32_t w0 = dpp_or0<0x00, 0xf>(wk), w1 = dpp_or0<0x55, 0xf>(wk), w2 = dpp_or0<0xaa, 0xf>(wk), w3 = dpp_or0<0xff, 0xf>(wk);
-                const uint32_t d = __builtin_amdgcn_perm(w1, w0, sel01) | __builtin_amdgcn_perm(w3, w2, sel23);
-                const uint32_t blk = 4u * k + qi;
-                if (valid && blk < nb_l) *reinterpret_cast<uint32_t *>(pl + (size_t)blk * B + (b & ~(size_t)3)) = d;
-            }
-            continue;
-        }
-        if (!valid) continue;
-        uint32_t *mp = masks + (size_t)plan.plane[lvl] * B + b;
-        if (plan.coarse[lvl]) {
-            mp[0] = m[0] | m[1] | m[2] | m[3] | m[4] | m[5];
-        } else {
-            // word k = blocks 4k..4k+3, bit 4 * j + (block & 3) for multisample j: a workgroup reads ONE word per sample
-            const uint32_t groups = (((lv.rows + (1u << plan.shift) - 1u) >> plan.shift) + 3u) / 4u;
-            for (uint32_t k = 0; k < groups; k++) {
-                uint32_t wk = 0u;
-#pragma unroll
-                for (uint32_t j = 0; j < 6; j++) wk |= ((m[j] >> (4u * k)) & 15u) << (4u * j);
-                mp[(size_t)k * B] = wk;
-            }
-        }
-    }
-    } while (false);
-    if (l1_partial) {
-        __syncthreads();
-        if (threadIdx.x < lvls.L)                           // fixed order: deterministic
-            l1_partial[(size_t)threadIdx.x * gridDim.x + blockIdx.x] =
-                ((s_l1[threadIdx.x][0] + s_l1[threadIdx.x][1]) + s_l1[threadIdx.x][2]) + s_l1[threadIdx.x][3];
-    }
-}
-template <bool TD = false>
-__global__ __launch_bounds__(256, 1) void k_cast_cache_masks_unwarped(UcnLevels lvls, RayInputs in, HexPattern hx, float std_scale,
-                                                          uint32_t N, uint32_t S, MaskPlan plan,
-                                                          const float *__restrict__ grad_features, GradStrides gs, uint32_t C,
-                                                          float *__restrict__ geom, uint32_t *__restrict__ masks,
-                                                          float *__restrict__ grad_level_major, uint32_t *__restrict__ task_counter,
-                                                          float *__restrict__ l1_partial) {
-    cast_cache_masks_body<TD, false>(lvls, in, hx, std_scale, N, S, plan, grad_features, gs, C, geom, masks, grad_level_major, task_counter,
-                                 l1_partial);
-}
 
 // Two rows of the block at once (the x0 / x0 + 1 corners of one (y, z) combination): both reads, then both compare-and-swaps
 // -- two LDS round trips where two lds_row_add calls make four.  A lane whose row is outside the block skips its half.
@@ -954,12 +746,12 @@ __device__ __forceinline__ void point_scatter_block(const UcnLevel &lv, A *__res
     }
 }
 
-template <uint32_t C, bool TD, bool WARP>
-__device__ __forceinline__ void march_features_bwd_blk_body(const UcnLevels &lvls, float *__restrict__ grad_table,
-                                                            const RayInputs &in, const HexPattern &hx, float std_scale, uint32_t N,
-                                                            uint32_t S, const GradStrides &gs, uint32_t rpb,
-                                                            const float *__restrict__ grad_features,
-                                                            const float *__restrict__ geom) {
+template <uint32_t C, bool TD = false, bool WARP = true>
+__global__ __launch_bounds__(1024) void k_march_features_bwd_blk(UcnLevels lvls, float *__restrict__ grad_table,
+                                                                 RayInputs in, HexPattern hx, float std_scale, uint32_t N,
+                                                                 uint32_t S, GradStrides gs, uint32_t rpb,
+                                                                 const float *__restrict__ grad_features,
+                                                                 const float *__restrict__ geom) {
     extern __shared__ float s_acc[];
     uint32_t task = blockIdx.x, lvl = 0, nb = 1, split = 1;
     for (;; lvl++) {
@@ -1019,80 +811,6 @@ __device__ __forceinline__ void march_features_bwd_blk_body(const UcnLevels &lvl
             else atomicAdd(gtab + i, v);
         }
     }
-}
-template <uint32_t C, bool TD = false>
-__global__ __launch_bounds__(1024) void k_march_features_bwd_blk(UcnLevels lvls, float *__restrict__ grad_table,
-                                                                 RayInputs in, HexPattern hx, float std_scale, uint32_t N,
-                                                                 uint32_t S, GradStrides gs, uint32_t rpb,
-                                                                 const float *__restrict__ grad_features,
-                                                                 const float *__restrict__ geom) {
-    extern __shared__ float s_acc[];
-    uint32_t task = blockIdx.x, lvl = 0, nb = 1, split = 1;
-    for (;; lvl++) {
-        nb = (lvls.lv[lvl].rows + rpb - 1) / rpb;
-        split = bwd_sample_split(nb);
-        if (task < nb * split || lvl + 1 == lvls.L) break;
-        task -= nb * split;
-    }
-    const UcnLevel lv = lvls.lv[lvl];
-    const uint32_t row_lo = (task / split) * rpb, part = task % split;
-    const uint32_t nrows = lv.rows - row_lo < rpb ? lv.rows - row_lo : rpb;
-    for (uint32_t i = threadIdx.x; i < nrows * C; i += 1024u) s_acc[i] = 0.0f;
-    __syncthreads();
-    const size_t B = (size_t)N * S;
-    // a level with few blocks (the dense coarse ones) is cut along the samples too: `split` workgroups per
-    // block, interleaved in units of 1024 samples; they share the block, so their flush is atomic
-    for (size_t b = (size_t)part * 1024u + threadIdx.x; b < B; b += (size_t)split * 1024u) {
-        const float *gp = grad_features + lvl * gs.level + b * gs.sample;
-        float gout[C];
-        bool nz = false;
-#pragma unroll
-        for (uint32_t c = 0; c < C; c++) {
-            gout[c] = gp[c * gs.chan] / 6.0f;                           // d(mean over the 6 multisamples)
-            nz |= gout[c] != 0.0f;
-        }
-        if (!nz) continue;
-        float u[6][3], rs[6];
-        if (geom) {                                   // k_cast_cache's planes: every task re-reads, nobody re-derives
-#pragma unroll
-            for (uint32_t j = 0; j < 6; j++) {
-                const float4 q = reinterpret_cast<const float4 *>(geom)[b * 6 + j];
-                u[j][0] = q.x; u[j][1] = q.y; u[j][2] = q.z; rs[j] = q.w;
-            }
-        } else {
-            const uint32_t ray = (uint32_t)(b / S), s = (uint32_t)(b - (size_t)ray * S);
-            float csum[3], tsum;
-            cast_sample<TD>(in, hx, std_scale, ray, s, S, u, rs, csum, tsum);
-        }
-        if (lv.hashed) {
-            if (lv.mask && lv.resolution <= 2048u) level_scatter_block<C, true, true, true>(lv, s_acc, row_lo, nrows, u, rs, gout);
-            else if (lv.mask) level_scatter_block<C, true, true, false>(lv, s_acc, row_lo, nrows, u, rs, gout);
-            else level_scatter_block<C, true, false, false>(lv, s_acc, row_lo, nrows, u, rs, gout);
-        } else if (lv.resolution <= 2048u) {
-            if (lv.mask) level_scatter_block<C, false, true, true>(lv, s_acc, row_lo, nrows, u, rs, gout);
-            else level_scatter_block<C, false, false, true>(lv, s_acc, row_lo, nrows, u, rs, gout);
-        } else {                                   // the strided fine levels of the uint32-wrap quirk: nothing to merge
-            if (lv.mask) level_scatter_block<C, false, true, false>(lv, s_acc, row_lo, nrows, u, rs, gout);
-            else level_scatter_block<C, false, false, false>(lv, s_acc, row_lo, nrows, u, rs, gout);
-        }
-    }
-    __syncthreads();
-    float *gtab = grad_table + ((size_t)lv.first_row + row_lo) * C;
-    for (uint32_t i = threadIdx.x; i < nrows * C; i += 1024u) {
-        const float v = s_acc[i];
-        if (v != 0.0f) {
-            if (split == 1) gtab[i] += v;
-            else atomicAdd(gtab + i, v);
-        }
-    }
-}
-template <uint32_t C, bool TD = false>
-__global__ __launch_bounds__(1024) void k_march_features_bwd_blk_unwarped(UcnLevels lvls, float *__restrict__ grad_table,
-                                                                 RayInputs in, HexPattern hx, float std_scale, uint32_t N,
-                                                                 uint32_t S, GradStrides gs, uint32_t rpb,
-                                                                 const float *__restrict__ grad_features,
-                                                                 const float *__restrict__ geom) {
-    march_features_bwd_blk_body<C, TD, false>(lvls, grad_table, in, hx, std_scale, N, S, gs, rpb, grad_features, geom);
 }
 
 // The same row-block ownership with COMPACTION.  A cell touches at most 8 of a level's 32 row blocks, a single
@@ -1725,10 +1443,10 @@ extern "C" int ucn_march_features_backward_row_blocks(const ucn_field_t *f, uint
     return (B > 0 && bwd_row_block_plan(lv, B, false, &plan) && bwd_row_block_plan(lv, B, true, &plan)) ? 1 : 0;
 }
 
-template <bool TD>
+template <bool TD, bool WARP>
 static int march_features_backward_launch(const ucn_field_t *f, const RayInputs &in, float std_scale, uint32_t N, uint32_t S,
                                           uint32_t levels_per_block, int layout, const float *grad_features,
-                                          float *grad_embeddings, float *workspace, ucn_stream_t stream, bool warp = true) {
+                                          float *grad_embeddings, float *workspace, ucn_stream_t stream) {
     UCN_REQUIRE(in.sdist && (TD || (in.near_ && in.far_)) && in.origins && in.dirs && in.basis && in.radii && grad_features &&
                 grad_embeddings, "march_features_backward: null pointer argument");
     UCN_REQUIRE((in.flip == nullptr) == (in.spin == nullptr), "march_features_backward: flip and spin come together");
@@ -1772,12 +1490,8 @@ static int march_features_backward_launch(const ucn_field_t *f, const RayInputs 
             float *glm = workspace + (24ull + plan.n_planes) * B;                               // level-major copy, / 6
             uint32_t *task_counter = reinterpret_cast<uint32_t *>(workspace + (24ull + plan.n_planes + (size_t)lv.L * lv.C) * B);
             float *l1_partial = reinterpret_cast<float *>(task_counter + 64);                   // [L][ceil(B / 256)] (fixed-point mode)
-            if (warp)
-                hipLaunchKernelGGL(k_cast_cache_masks<TD>, dim3(ucn_div_up(B, 256)), dim3(256), 0, st, lv, in, hx, std_scale, N, S, plan,
-                                   grad_features, gs, lv.C, workspace, masks, prediv ? nullptr : glm, task_counter, fixed ? l1_partial : nullptr);
-            else
-                hipLaunchKernelGGL(k_cast_cache_masks_unwarped<TD>, dim3(ucn_div_up(B, 256)), dim3(256), 0, st, lv, in, hx, std_scale, N, S, plan,
-                                   grad_features, gs, lv.C, workspace, masks, prediv ? nullptr : glm, task_counter, fixed ? l1_partial : nullptr);
+            hipLaunchKernelGGL((k_cast_cache_masks<TD, WARP>), dim3(ucn_div_up(B, 256)), dim3(256), 0, st, lv, in, hx, std_scale, N, S, plan,
+                               grad_features, gs, lv.C, workspace, masks, prediv ? nullptr : glm, task_counter, fixed ? l1_partial : nullptr);
             const float *glv = prediv ? grad_features : glm;                                    // [L][B][C], / 6
             const uint32_t cus = device_cu_count();
             ucn_for_level_dim(lv.C, [&](auto cc) {
@@ -1800,18 +1514,12 @@ static int march_features_backward_launch(const ucn_field_t *f, const RayInputs 
         }
         UCN_REQUIRE(!prediv, "march_features_backward: layout 4 (pre-divided level-major gradient) is the compacted row-block kernel's input; this call would take a fallback");
         if (blocks <= 64u * lv.L) {
-            if (workspace && warp)
-                hipLaunchKernelGGL(k_cast_cache<TD>, dim3(ucn_div_up(B, 256)), dim3(256), 0, st, in, hx, std_scale, N, S, workspace);
-            else if (workspace)
-                hipLaunchKernelGGL(k_cast_cache_unwarped<TD>, dim3(ucn_div_up(B, 256)), dim3(256), 0, st, in, hx, std_scale, N, S, workspace);
+            if (workspace)
+                hipLaunchKernelGGL((k_cast_cache<TD, WARP>), dim3(ucn_div_up(B, 256)), dim3(256), 0, st, in, hx, std_scale, N, S, workspace);
             ucn_for_level_dim(lv.C, [&](auto cc) {
                 constexpr uint32_t CC = decltype(cc)::value;
-                if (warp)
-                    hipLaunchKernelGGL((k_march_features_bwd_blk<CC, TD>), dim3(tasks), dim3(1024), (size_t)rpb * CC * 4, st, lv,
-                                       grad_embeddings, in, hx, std_scale, N, S, gs, rpb, grad_features, workspace);
-                else
-                    hipLaunchKernelGGL((k_march_features_bwd_blk_unwarped<CC, TD>), dim3(tasks), dim3(1024), (size_t)rpb * CC * 4, st, lv,
-                                       grad_embeddings, in, hx, std_scale, N, S, gs, rpb, grad_features, workspace);
+                hipLaunchKernelGGL((k_march_features_bwd_blk<CC, TD, WARP>), dim3(tasks), dim3(1024), (size_t)rpb * CC * 4, st, lv,
+                                   grad_embeddings, in, hx, std_scale, N, S, gs, rpb, grad_features, workspace);
             });
             UCN_LAUNCH_CHECK("march_features_backward (row blocks)");
             return 0;
@@ -1822,12 +1530,8 @@ static int march_features_backward_launch(const ucn_field_t *f, const RayInputs 
     UCN_REQUIRE(!prediv, "march_features_backward: layout 4 is a row-block layout (levels_per_block = 0 with a workspace)");
     const dim3 grid(ucn_div_up(B, 256), ucn_div_up(lv.L, levels_per_block));
     ucn_for_level_dim(lv.C, [&](auto cc) {
-        if (warp)
-            hipLaunchKernelGGL((k_march_features_bwd<decltype(cc)::value, TD>), grid, dim3(256), 0, st, lv, grad_embeddings, in, hx,
-                               std_scale, N, S, levels_per_block, layout, grad_features);
-        else
-            hipLaunchKernelGGL((k_march_features_bwd_unwarped<decltype(cc)::value, TD>), grid, dim3(256), 0, st, lv, grad_embeddings, in,
-                               hx, std_scale, N, S, levels_per_block, layout, grad_features);
+        hipLaunchKernelGGL((k_march_features_bwd<decltype(cc)::value, TD, WARP>), grid, dim3(256), 0, st, lv, grad_embeddings, in, hx,
+                           std_scale, N, S, levels_per_block, layout, grad_features);
     });
     UCN_LAUNCH_CHECK("march_features_backward");
     return 0;
@@ -1843,11 +1547,14 @@ extern "C" int ucn_march_features_backward_warp(const ucn_field_t *f, const floa
     UCN_REQUIRE((near_ == nullptr) == (far_ == nullptr),
                 "march_features_backward: near and far come together (both NULL: metric fenceposts)");
     const RayInputs in{fenceposts, near_, far_, origins, directions, basis, radii, flip, spin};
-    if (near_ == nullptr)
-        return march_features_backward_launch<true>(f, in, std_scale, N, S, levels_per_block, layout, grad_features, grad_embeddings,
-                                                    workspace, stream, warp != 0);
-    return march_features_backward_launch<false>(f, in, std_scale, N, S, levels_per_block, layout, grad_features, grad_embeddings,
-                                                 workspace, stream, warp != 0);
+    int rc = 0;
+    ucn_for_bool(near_ == nullptr, [&](auto td) {
+        ucn_for_bool(warp != 0, [&](auto w) {
+            rc = march_features_backward_launch<decltype(td)::value, decltype(w)::value>(f, in, std_scale, N, S, levels_per_block, layout,
+                                                                                         grad_features, grad_embeddings, workspace, stream);
+        });
+    });
+    return rc;
 }
 
 extern "C" int ucn_march_features_backward(const ucn_field_t *f, const float *sdist, const float *near_, const float *far_,

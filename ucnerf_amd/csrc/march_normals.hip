@@ -173,7 +173,10 @@ __device__ __forceinline__ void store_normal(const float (&acc)[3], uint32_t G, 
 }
 
 // layout: 0 = gfeat [L][N*S][C] with b = ray*S + s; 2 = [L][S*N][C] with b = s*N + ray (ucn_march_features'); outputs [ray][s]
-template <uint32_t C, bool TD>
+// WARP = false (MLP.warp_fn = None): the same kernel on the uncontracted Gaussians: d raw / d x_j = (1/G) gu_j / 2, no Jacobian and
+// nothing through the std (it does not depend on the mean); a sample with all six points outside the cube gets raw_grad = +0 and
+// normals = -0.
+template <uint32_t C, bool TD, bool WARP = true>
 __global__ __launch_bounds__(256) void k_march_density_grad(UcnLevels lvls, const float *__restrict__ table, RayInputs in,
                                                             HexPattern hx, float std_scale, uint32_t N, uint32_t S, int layout,
                                                             const float *__restrict__ gfeat, float *__restrict__ raw_grad_out,
@@ -188,43 +191,13 @@ __global__ __launch_bounds__(256) void k_march_density_grad(UcnLevels lvls, cons
     float pr[6 * UCN_CAST_PROBE_FLOATS];                            // the world-space means (registers: every index is a constant)
     float *probe = pr;
     __builtin_assume(probe != nullptr);                             // folds cast_sample's `if (probe)`: pr stays in registers
-    cast_sample<TD>(in, hx, std_scale, ray, s, S, u, rs, csum, tsum, probe);
+    cast_sample<TD, WARP>(in, hx, std_scale, ray, s, S, u, rs, csum, tsum, probe);
     float gu[6][3], gsig[6];
     density_grad_levels<C>(lvls, table, gfeat, B, b, u, rs, 6, gu, gsig);
     float acc[3] = {0.0f, 0.0f, 0.0f};
 #pragma unroll
     for (uint32_t j = 0; j < 6; j++)
-        point_to_world(pr[j * UCN_CAST_PROBE_FLOATS], pr[j * UCN_CAST_PROBE_FLOATS + 1], pr[j * UCN_CAST_PROBE_FLOATS + 2], true, gu[j],
-                       gsig[j], acc);
-    store_normal(acc, 6, raw_grad_out, normals_out, (size_t)ray * S + s);
-}
-
-// MLP.warp_fn = None: the same kernel on the uncontracted Gaussians: d raw / d x_j = (1/G) gu_j / 2, no Jacobian and nothing through the
-// std (it does not depend on the mean); a sample with all six points outside the cube gets raw_grad = +0 and normals = -0.  A
-// kernel of its own beside the warped one, whose body stays as it was: as a shared body template with the warp as an argument the
-// warped instantiation came out in another schedule (profiles/unwarped/isa_identity.txt).
-template <uint32_t C, bool TD>
-__global__ __launch_bounds__(256) void k_march_density_grad_unwarped(UcnLevels lvls, const float *__restrict__ table, RayInputs in,
-                                                            HexPattern hx, float std_scale, uint32_t N, uint32_t S, int layout,
-                                                            const float *__restrict__ gfeat, float *__restrict__ raw_grad_out,
-                                                            float *__restrict__ normals_out) {
-    const size_t B = (size_t)N * S;
-    const size_t b = (size_t)blockIdx.x * 256u + threadIdx.x;
-    if (b >= B) return;
-    uint32_t ray, s;
-    if (layout == 2) { s = (uint32_t)(b / N); ray = (uint32_t)(b - (size_t)s * N); }
-    else { ray = (uint32_t)(b / S); s = (uint32_t)(b - (size_t)ray * S); }
-    float u[6][3], rs[6], csum[3], tsum;
-    float pr[6 * UCN_CAST_PROBE_FLOATS];                            // the world-space means (registers: every index is a constant)
-    float *probe = pr;
-    __builtin_assume(probe != nullptr);                             // folds cast_sample's `if (probe)`: pr stays in registers
-    cast_sample<TD, false>(in, hx, std_scale, ray, s, S, u, rs, csum, tsum, probe);
-    float gu[6][3], gsig[6];
-    density_grad_levels<C>(lvls, table, gfeat, B, b, u, rs, 6, gu, gsig);
-    float acc[3] = {0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (uint32_t j = 0; j < 6; j++)
-        point_to_world(pr[j * UCN_CAST_PROBE_FLOATS], pr[j * UCN_CAST_PROBE_FLOATS + 1], pr[j * UCN_CAST_PROBE_FLOATS + 2], false, gu[j],
+        point_to_world(pr[j * UCN_CAST_PROBE_FLOATS], pr[j * UCN_CAST_PROBE_FLOATS + 1], pr[j * UCN_CAST_PROBE_FLOATS + 2], WARP, gu[j],
                        gsig[j], acc);
     store_normal(acc, 6, raw_grad_out, normals_out, (size_t)ray * S + s);
 }
@@ -310,13 +283,13 @@ extern "C" int ucn_march_density_grad_warp(const ucn_field_t *f, const float *fe
     const dim3 grid(ucn_div_up(B, 256));
     ucn_for_level_dim(lv.C, [&](auto cc) {
         constexpr uint32_t CC = decltype(cc)::value;
-#define UCN_DG(KERNEL, TDV)                                                                                               \
-    hipLaunchKernelGGL((KERNEL<CC, TDV>), grid, dim3(256), 0, (hipStream_t)stream, lv, f->embeddings, in, hx, std_scale, N, S, layout, \
-                       gfeat, raw_grad_out, normals_out)
-        if (warp && td) UCN_DG(k_march_density_grad, true);
-        else if (warp) UCN_DG(k_march_density_grad, false);
-        else if (td) UCN_DG(k_march_density_grad_unwarped, true);
-        else UCN_DG(k_march_density_grad_unwarped, false);
+#define UCN_DG(TDV, WARPV)                                                                                                \
+    hipLaunchKernelGGL((k_march_density_grad<CC, TDV, WARPV>), grid, dim3(256), 0, (hipStream_t)stream, lv, f->embeddings, in, hx,    \
+                       std_scale, N, S, layout, gfeat, raw_grad_out, normals_out)
+        if (warp && td) UCN_DG(true, true);
+        else if (warp) UCN_DG(false, true);
+        else if (td) UCN_DG(true, false);
+        else UCN_DG(false, false);
 #undef UCN_DG
     });
     UCN_LAUNCH_CHECK("march_density_grad");

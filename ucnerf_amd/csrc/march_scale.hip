@@ -55,10 +55,10 @@ __device__ __forceinline__ void scale_features_store(const ScaleLevels &sl, cons
 
 // WARP = false (MLP.warp_fn = None): the damping of the uncontracted std.  A point outside the unit cube adds no grid feature but
 // keeps its erf weight here -- models.py:505 averages the weights over all six -- so nothing in this unit looks at u.
-template <uint32_t C, bool TD, bool WARP>
-__device__ __forceinline__ void march_scale_features_body(const ScaleLevels &sl, const float *__restrict__ level_scale,
-                                                          const RayInputs &in, const HexPattern &hx, float std_scale, uint32_t N,
-                                                          uint32_t S, int layout, float *__restrict__ scale_out) {
+template <uint32_t C, bool TD, bool WARP = true>
+__global__ __launch_bounds__(256) void k_march_scale_features(ScaleLevels sl, const float *__restrict__ level_scale, RayInputs in,
+                                                              HexPattern hx, float std_scale, uint32_t N, uint32_t S, int layout,
+                                                              float *__restrict__ scale_out) {
     const size_t B = (size_t)N * S;
     const size_t b = (size_t)blockIdx.x * 256u + threadIdx.x;
     if (b >= B) return;
@@ -68,18 +68,6 @@ __device__ __forceinline__ void march_scale_features_body(const ScaleLevels &sl,
     float u[6][3], rs[6], csum[3], tsum;
     cast_sample<TD, WARP>(in, hx, std_scale, ray, s, S, u, rs, csum, tsum);
     scale_features_store<C>(sl, level_scale, rs, 6, B, b, scale_out, layout == 1);
-}
-template <uint32_t C, bool TD>
-__global__ __launch_bounds__(256) void k_march_scale_features(ScaleLevels sl, const float *__restrict__ level_scale, RayInputs in,
-                                                              HexPattern hx, float std_scale, uint32_t N, uint32_t S, int layout,
-                                                              float *__restrict__ scale_out) {
-    march_scale_features_body<C, TD, true>(sl, level_scale, in, hx, std_scale, N, S, layout, scale_out);
-}
-template <uint32_t C, bool TD>
-__global__ __launch_bounds__(256) void k_march_scale_features_unwarped(ScaleLevels sl, const float *__restrict__ level_scale,
-                                                                       RayInputs in, HexPattern hx, float std_scale, uint32_t N,
-                                                                       uint32_t S, int layout, float *__restrict__ scale_out) {
-    march_scale_features_body<C, TD, false>(sl, level_scale, in, hx, std_scale, N, S, layout, scale_out);
 }
 
 template <uint32_t C>
@@ -151,10 +139,9 @@ ScaleLevels scale_levels(const UcnLevels &lv) {
 
 }  // namespace
 
-template <bool TD>
+template <bool TD, bool WARP>
 static int march_scale_features_launch(const ucn_field_t *f, const RayInputs &in, float std_scale, uint32_t N, uint32_t S,
-                                       const float *level_scale, int layout, float *scale_out, ucn_stream_t stream,
-                                       bool warp = true) {
+                                       const float *level_scale, int layout, float *scale_out, ucn_stream_t stream) {
     UCN_REQUIRE(N == 0 || (in.sdist && (TD || (in.near_ && in.far_)) && in.origins && in.dirs && in.basis && in.radii && level_scale &&
                            scale_out), "march_scale_features: null pointer argument");
     UCN_REQUIRE((in.flip == nullptr) == (in.spin == nullptr), "march_scale_features: flip and spin come together");
@@ -168,12 +155,8 @@ static int march_scale_features_launch(const ucn_field_t *f, const RayInputs &in
     const HexPattern hx = make_hex();
     const dim3 grid(ucn_div_up(B, 256));
     ucn_for_level_dim(lv.C, [&](auto cc) {
-        if (warp)
-            hipLaunchKernelGGL((k_march_scale_features<decltype(cc)::value, TD>), grid, dim3(256), 0, (hipStream_t)stream, sl, level_scale,
-                               in, hx, std_scale, N, S, layout, scale_out);
-        else
-            hipLaunchKernelGGL((k_march_scale_features_unwarped<decltype(cc)::value, TD>), grid, dim3(256), 0, (hipStream_t)stream, sl,
-                               level_scale, in, hx, std_scale, N, S, layout, scale_out);
+        hipLaunchKernelGGL((k_march_scale_features<decltype(cc)::value, TD, WARP>), grid, dim3(256), 0, (hipStream_t)stream, sl,
+                           level_scale, in, hx, std_scale, N, S, layout, scale_out);
     });
     UCN_LAUNCH_CHECK("march_scale_features");
     return 0;
@@ -188,8 +171,14 @@ extern "C" int ucn_march_scale_features_warp(const ucn_field_t *f, const float *
     UCN_REQUIRE(N == 0 || (near_ == nullptr) == (far_ == nullptr),
                 "march_scale_features: near and far come together (both NULL: metric fenceposts)");
     const RayInputs in{fenceposts, near_, far_, origins, directions, basis, radii, flip, spin};
-    if (near_ == nullptr) return march_scale_features_launch<true>(f, in, std_scale, N, S, level_scale, layout, scale_out, stream, warp != 0);
-    return march_scale_features_launch<false>(f, in, std_scale, N, S, level_scale, layout, scale_out, stream, warp != 0);
+    int rc = 0;
+    ucn_for_bool(near_ == nullptr, [&](auto td) {
+        ucn_for_bool(warp != 0, [&](auto w) {
+            rc = march_scale_features_launch<decltype(td)::value, decltype(w)::value>(f, in, std_scale, N, S, level_scale, layout, scale_out,
+                                                                                      stream);
+        });
+    });
+    return rc;
 }
 
 extern "C" int ucn_march_scale_features(const ucn_field_t *f, const float *sdist, const float *near_, const float *far_,

@@ -82,3 +82,9 @@ static inline void ucn_for_level_dim(uint32_t C, Fn &&fn) {
         case 8: fn(std::integral_constant<uint32_t, 8>{}); break;
     }
 }
+// Host: a run-time flag as a compile-time constant:  ucn_for_bool(warp, [&](auto w) { launch k<..., decltype(w)::value> ... });
+template <typename Fn>
+static inline void ucn_for_bool(bool v, Fn &&fn) {
+    if (v) fn(std::bool_constant<true>{});
+    else fn(std::bool_constant<false>{});
+}
