@@ -667,6 +667,36 @@ int ucn_spherical_rays(const double *camtoworld, uint32_t width, uint32_t height
                        float *directions, float *viewdirs, float *radii, float *imageplane, float *cam_dirs, float *near_out,
                        float *far_out, float *lossmult_out, float *cam_idx_out, ucn_stream_t stream);
 
+/* ------------------------------------------------- batches from a device-resident dataset (SURVEY 8 f1 + f3)
+ * ref: datasets.py:386-476 _make_ray_batch, both branches.  One launch, one thread per ray.  Added within ABI 32: no existing
+ * signature changes.
+ * Each ray has a CAST triple (cam_cast, x_cast, y_cast) that drives ray generation, exactly ucn_generate_rays_model (same
+ * per-ray code, same bits), and a LOOK-UP triple (cam_look, x_look, y_look) that drives the image gathers; the virtual-pose
+ * branch (:457-473) casts through one camera / pixel and takes its supervision from another.  All DEVICE int32 [n_rays].
+ * cam_look / x_look / y_look all NULL = the look-up triple is the cast triple.  x_cast / y_cast both NULL = every pixel of a
+ * width x height frame in 'xy' meshgrid order (n_rays = width * height).  cam_cast NULL = cam_cast_scalar for every ray.
+ * pixtocams DEVICE double [n_cams,3,3], camtoworlds DEVICE double [n_cams,3,4]; n_cams may exceed n_images (the reference
+ * appends the virtual cameras, datasets.py:867-870).
+ * Planes: plane_src_host / plane_dst_host / plane_channels_host = HOST [n_planes] tables, n_planes <= UCN_BATCH_MAX_PLANES;
+ * plane p is a DEVICE float32 [n_images, height, width, C_p] array, C_p in 1..4, and its output DEVICE float32 [n_rays, C_p] =
+ * plane[cam_look, y_look, x_look, :] copied bit for bit.
+ * Columns (each may be NULL): near_out / far_out [n,1] = near_ / far_; cam_idx_out [n,1] = the cast camera; lossmult_out =
+ * [n,3] raw_utils.py:38-46 pixels_to_bayer_mask of the look-up pixel with UCN_BATCH_BAYER_MASK in flags, else [n,C] a copy of
+ * lossmult_in (DEVICE float32 [n, lossmult_channels], 1..4) when that is given, else [n,1] ones.
+ * status DEVICE uint32[2] | NULL, zeroed by the caller: a look-up index outside [0, n_images) x [0, height) x [0, width) reads
+ * nothing, that ray's plane outputs are NaN and status[0] becomes 1; a cast camera outside [0, n_cams) reads nothing, that
+ * ray's origins .. cam_dirs are NaN and status[1] becomes 1.  n_rays == 0 returns 0 without a launch. */
+#define UCN_BATCH_MAX_PLANES 4
+#define UCN_BATCH_BAYER_MASK 1
+int ucn_train_batch(const int32_t *cam_cast, int32_t cam_cast_scalar, const int32_t *x_cast, const int32_t *y_cast,
+                    const int32_t *cam_look, const int32_t *x_look, const int32_t *y_look, const double *pixtocams,
+                    const double *camtoworlds, uint32_t n_cams, uint32_t n_images, uint32_t height, uint32_t width,
+                    uint32_t n_rays, const float *const *plane_src_host, float *const *plane_dst_host,
+                    const uint32_t *plane_channels_host, uint32_t n_planes, float near_, float far_,
+                    const float *lossmult_in, uint32_t lossmult_channels, int flags, float *origins, float *directions,
+                    float *viewdirs, float *radii, float *imageplane, float *cam_dirs, float *near_out, float *far_out,
+                    float *lossmult_out, float *cam_idx_out, uint32_t *status, int camera_model, ucn_stream_t stream);
+
 /* ------------------------------------------------- sky layer + colour correction
  * ref: models.py:326-337,743-904 (sky NeRF, 120 samples, 8x256 MLP) and
  * extrinsic_optimizer.py:4-48 + models.py:339-363 (per-camera 3x4 affine). */

@@ -124,9 +124,10 @@ globals().update(_CONSTANTS)        # UCN_TABLE_F16 -> TABLE_F16, ...; ABI_VERSI
 UcnField, UcnSky, UcnSkyTrain = _STRUCTS["ucn_field_t"], _STRUCTS["ucn_sky_t"], _STRUCTS["ucn_sky_train_t"]
 SIGNATURES = {name: args for name, (_, args) in _PROTOTYPES.items()}      # name -> argtypes
 
-# Entry points added without an ABI bump: host-side probes that no product path calls.  An older build of the same ABI
-# loaded through UCN_LIB_PATH may lack them; every other symbol is required.
-_ADDED_WITHIN_ABI = {"ucn_level_groups_probe"}
+# Entry points added without an ABI bump: a host-side probe that no product path calls, and the batch assembler of
+# internal/datasets.py, which no earlier path calls.  An older build of the same ABI loaded through UCN_LIB_PATH may lack them
+# (calling one there is an AttributeError, not a fallback); every other symbol is required.
+_ADDED_WITHIN_ABI = {"ucn_level_groups_probe", "ucn_train_batch"}
 
 _lib = None
 

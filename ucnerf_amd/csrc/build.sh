@@ -6,7 +6,7 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -Wall -Wno-unused-function"
 mkdir -p _obj
 pids=()
-for f in grid_op march_ray march_features march_features_bwd march_scale march_normals pred_normals ref_colour gemm_f32 gemm_h3 field_mlp field_mlp_h heads heads_train sky sky_train wgrad rays train_ops warp field_train prop_train tsdf mesh metrics colour_correct; do
+for f in grid_op march_ray march_features march_features_bwd march_scale march_normals pred_normals ref_colour gemm_f32 gemm_h3 field_mlp field_mlp_h heads heads_train sky sky_train wgrad rays batch train_ops warp field_train prop_train tsdf mesh metrics colour_correct; do
   stale=0
   for h in "$f.hip" *.h ../../include/ucnerf_march.h; do
     if [ ! -f "_obj/$f.o" ] || [ "$h" -nt "_obj/$f.o" ]; then stale=1; fi

@@ -16,19 +16,9 @@
 // reference's operation order (explicit mul / add, -ffp-contract=off; IEEE double division and sqrt), and rounds once
 // at the store -- the float32 batch is bit-identical to the reference's (tests/golden/rays.npz).  The kernel is a pure
 // streaming write: 68 B per ray (76 with the image plane) out, 8 B in when pixel coordinates are given.
-#include "ucn_common.h"
+#include "rays_core.h"
 
 namespace {
-
-struct RayOut {
-    float *origins, *directions, *viewdirs, *radii, *imageplane, *cam_dirs, *near_, *far_, *lossmult, *cam_idx;
-};
-
-__device__ __forceinline__ void matvec3(const double *__restrict__ A, uint32_t ld, double x, double y, double z, double (&o)[3]) {
-#pragma unroll
-    for (int i = 0; i < 3; i++) o[i] = (A[i * ld + 0] * x + A[i * ld + 1] * y) + A[i * ld + 2] * z;
-}
-__device__ __forceinline__ double norm3(double x, double y, double z) { return sqrt((x * x + y * y) + z * z); }
 
 // MODEL 0 = perspective, 1 = panorama (camera_utils.py:507-510, camtype == 'panoroma')
 template <int MODEL>
@@ -39,41 +29,9 @@ __global__ __launch_bounds__(256) void k_generate_rays(const int32_t *__restrict
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     const int32_t cam = cam_idx ? cam_idx[i] : cam_scalar;
-    const double *P = pixtocams + (size_t)cam * 9, *M = camtoworlds + (size_t)cam * 12;
     const double x = (double)(pix_x ? pix_x[i] : (int32_t)(i % width));          // camera_utils.py:368-370 'xy' meshgrid
     const double y = (double)(pix_y ? pix_y[i] : (int32_t)(i / width));
-    // pixel centre and its +1 neighbours in x and y (:487-495), inverse intrinsics (:501), OpenCV -> OpenGL (:531)
-    double c[3][3], d[3][3];
-    matvec3(P, 3, x + 0.5, y + 0.5, 1.0, c[0]);
-    matvec3(P, 3, (x + 1.0) + 0.5, y + 0.5, 1.0, c[1]);
-    matvec3(P, 3, x + 0.5, (y + 1.0) + 0.5, 1.0, c[2]);
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        if constexpr (MODEL == 1) {                                              // the image plane bent onto a cylinder (:507-510)
-            sincos(c[k][0], &c[k][0], &c[k][2]);                                 // one argument reduction for both
-        }
-        c[k][1] = -c[k][1];
-        c[k][2] = -c[k][2];
-        matvec3(M, 4, c[k][0], c[k][1], c[k][2], d[k]);                          // camera rotation (:538)
-    }
-    const double nd = norm3(d[0][0], d[0][1], d[0][2]);
-    const double dxn = norm3(d[1][0] - d[0][0], d[1][1] - d[0][1], d[1][2] - d[0][2]);      // :548-549
-    const double dyn = norm3(d[2][0] - d[0][0], d[2][1] - d[0][1], d[2][2] - d[0][2]);
-    const double radius = (0.5 * (dxn + dyn)) * 2.0 / 3.4641016151377544;        // :562, np.sqrt(12)
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        out.origins[(size_t)i * 3 + k] = (float)M[k * 4 + 3];
-        out.directions[(size_t)i * 3 + k] = (float)d[0][k];
-        out.viewdirs[(size_t)i * 3 + k] = (float)(d[0][k] / nd);                 // :544
-        out.cam_dirs[(size_t)i * 3 + k] = (float)(-M[k * 4 + 2]);               // datasets.py:446
-    }
-    out.radii[i] = (float)radius;
-    if (out.imageplane) {
-        out.imageplane[(size_t)i * 2 + 0] = (float)c[0][0];
-        out.imageplane[(size_t)i * 2 + 1] = (float)c[0][1];
-    }
-    if (out.near_) out.near_[i] = near_v;
-    if (out.far_) out.far_[i] = far_v;
+    ray_from_pixel<MODEL>(i, cam, x, y, pixtocams, camtoworlds, near_v, far_v, out);   // rays_core.h, shared with batch.hip
     if (out.lossmult) out.lossmult[i] = 1.0f;
     if (out.cam_idx) out.cam_idx[i] = (float)cam;
 }
